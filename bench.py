@@ -3,7 +3,7 @@
 bench.py -- S^3 hot path on MI355X: snapshot interpolation throughput (+ refine wall-clock) on the synthetic
 cylinder3D_Re3900 workload of BASELINE.json / SURVEY.md 8(d).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
 
 A *step* is one pass of the interpolation hot path over one batch of synthetic snapshots already resident in HBM IN THE FORM
 THE API RECEIVES IT (interpolate_data(w, idx, data), reference export.py:446-468): a dense tensor [N_points, T_batch] fp32 with
@@ -27,6 +27,10 @@ Multi-GPU (one process per GPU; the collectives run inside libs3hip.so on RCCL).
   KNN cache / plan of its shard and only the source rows that shard references, and interpolates the same snapshot
   batch -- no data-path collective; total work is fixed ("scaling": "strong").  `--shard snapshots` gives every rank
   all cells and its own snapshot batches instead ("weak").
+
+`--dump-outputs DIR` writes what the timed path computed in its LAST timed step, as a caller of that path receives it, to
+DIR/<name>.npy (dump_outputs: at most 64 MB; a fixed, seeded sample of the rows where the output is larger).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP events on the launch stream: mean, min, median, max
 per launch, and the identity of the device they were taken on) and, at N = 1:
@@ -646,6 +650,26 @@ def device_resident_input(x, centers, k, t_list, bare_ms):
     return out
 
 
+DUMP_BYTES = 64_000_000          # --dump-outputs: the most a run writes, all files together (npy headers included)
+
+
+def dump_outputs(directory, **arrays):
+    """write each array as DIR/<name>.npy; all of them must be float32 / float64 and fit DUMP_BYTES together"""
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes + 128 for a in arrays.values()) <= DUMP_BYTES
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
+def sampled_rows(n_rows, row_bytes):
+    """the fixed, seeded sample of row ids (ascending) a dump takes of an output of n_rows rows: every row where they fit"""
+    n = min(n_rows, (DUMP_BYTES - 4096) // row_bytes)
+    if n == n_rows:
+        return np.arange(n_rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(n_rows, size=n, replace=False))
+
+
 def bench_svd(args, json_fd):
     """`--workload svd`: the weighted Gram matrix of the interpolated snapshot matrix on the f64 matrix cores
     (s3_weighted_gram: the kernel of utils.compute_svd, reference utils.py:302-346) at the bench grid's size -- 461 130 cells x
@@ -665,9 +689,12 @@ def bench_svd(args, json_fd):
     pt.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        svd.weighted_gram(x, mean, w)
+        gram = svd.weighted_gram(x, mean, w)
     pt.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, weighted_gram=gram.cpu().numpy())       # [T, T] f64: 8 MB at T = 1000
+    del gram
     flops = float(n) * t * (t + 1)
     st = ms_stats(ms)
     t1 = time.perf_counter()
@@ -858,6 +885,19 @@ def launch_ranks(args, argv):
     return 1
 
 
+def without_dump_outputs(argv):
+    """argv minus `--dump-outputs DIR` / `--dump-outputs=DIR`"""
+    out, skip = [], False
+    for a in argv:
+        if skip:
+            skip = False
+        elif a == "--dump-outputs":
+            skip = True
+        elif not a.startswith("--dump-outputs="):
+            out.append(a)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -878,7 +918,14 @@ def main():
                          "(leaf-cell shards, default) or all cells for its own snapshot batches")
     ap.add_argument("--direct", action="store_true", help="time the direct gather kernel (s3_interp) instead of the "
                     "planned LDS-tiled kernel (s3_interp_planned)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (at most 64 MB: a fixed, seeded "
+                         "sample of the rows of a larger output)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))            # no launcher around us: start (and watch) the N ranks ourselves
@@ -906,6 +953,7 @@ def main():
     if rank == 0 and world == 1 and not args.no_traffic and args.workload != "svd" and not args.direct:
         # (also before anything initialises the GPU: the passes are child processes of this one)
         child_argv = [a for a in sys.argv[1:] if a not in ("--no-cpu-baseline", "--no-batches", "--no-pitched-copy")]
+        child_argv = without_dump_outputs(child_argv)             # (the PMC passes write no outputs)
         measured = optional_leg("measure_traffic", lambda: measure_traffic(child_argv, "interp_planned"))
         if isinstance(measured, dict) and "error" in measured:
             measured = None
@@ -1034,6 +1082,12 @@ def main():
     elapsed = comm.allreduce_max(time.perf_counter() - t0)
     launch_ms = [a.elapsed_time(b) for a, b in ev]                       # HIP events on the launch stream, per launch
     kernel_ms = float(np.mean(launch_ms))
+    if args.dump_outputs and rank == 0 and not args.traffic_child:
+        # the last timed step's result, as interpolate_data's caller gets it: out [cells, n_comp * T] f64 (this rank's cells), a seeded
+        # sample of its rows where it exceeds the budget, with the ids and centres of the cells sampled
+        rows = sampled_rows(nc, row_len * 8 + 4 * 8)
+        dump_outputs(args.dump_outputs, interpolated=out[pt.from_numpy(rows).to(out.device)].cpu().numpy(),
+                     cell_ids=rows.astype(np.float64), cell_centers=np.ascontiguousarray(my_centers[rows], dtype=np.float64))
 
     # the same launch on the pitched, compacted copy of the referenced rows (Hilbert order, whole 128-byte lines per row:
     # the layout ExportData uploads HOST batches into -- rounds 1-3 quoted the headline on it)

@@ -16,13 +16,14 @@ The one documented deviation: with ``write_new_file_for_each_field=True`` the re
 
 CPU tests run the host logic on oracle-backed stand-ins for the device entry points (as tests/test_export_host_logic.py does);
 the ``-m gpu`` tests run grid generation + export on the HIP path.  Files are read back with the independent stand-in binding,
-not with the package's own HDF5 layer.  Where the reference is present (development container), its ``Dataloader`` and
-``XDMFWriter`` additionally read / describe files THIS build wrote (``tests/golden/ref_judge.py``, own process).
+not with the package's own HDF5 layer.  The reference's ``Dataloader`` and ``XDMFWriter`` also read / describe files THIS build
+writes, and its ``Datawriter`` and ``ExportData`` write files of their own: their verdicts are stored under
+``tests/golden/judged/`` (``tests/golden/gen_judged.py``, which runs ``tests/golden/ref_judge.py``), each beside the digest of the
+file it judged, so that the file this build writes now is the one the reference saw.
 """
+import hashlib
 import json
 import os
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -35,7 +36,7 @@ from sparsespatialsampling_amd import h5io
 from tests.test_export_host_logic import _cpu_ops
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-HAVE_REFERENCE = os.path.isdir("/root/reference/sparseSpatialSampling")
+JUDGED = os.path.join(GOLDEN, "judged")
 pytestmark = pytest.mark.skipif(h5io.native_lib() is None, reason="libs3h5.so not available")
 
 
@@ -62,6 +63,15 @@ def inventory(path):
     with h5ref.File(path, "r") as f:
         walk(f, "")
     return out
+
+
+def file_digest(path):
+    """sha256 over a file's inventory (dataset names in order, dtypes, shapes, values)"""
+    h = hashlib.sha256()
+    for name, a in inventory(path):
+        h.update(f"{name}:{a.dtype.str}:{a.shape};".encode())
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
 
 
 def compare_file(got, want, label):
@@ -187,12 +197,11 @@ def test_export_matches_reference_files_gpu(tmp_path, tag):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# the reference's loader / XDMF writer on files this build wrote (development container only)
+# the reference's loader / XDMF writer on files this build writes (their verdicts: tests/golden/judged/, gen_judged.py)
 # ----------------------------------------------------------------------------------------------------------------------
-def _judge(*args):
-    res = subprocess.run([sys.executable, os.path.join(GOLDEN, "ref_judge.py"), *map(str, args)], capture_output=True, text=True,
-                         timeout=300)
-    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+XDMF_PARAMS = [(2, True, True, 0), (3, True, True, 0), (3, False, True, 0), (2, True, False, 0), (2, False, False, 0), (3, True, True, 1),
+               (2, False, True, 1)]
+XDMF_CASES = {f"{d}-{with_data}-{with_const}-{mixed}": (d, with_data, with_const, mixed) for d, with_data, with_const, mixed in XDMF_PARAMS}
 
 
 def _write_with_build(directory, d, n_t, with_data=True, with_const=True, seed=0):
@@ -226,13 +235,11 @@ def _write_with_build(directory, d, n_t, with_data=True, with_const=True, seed=0
     return want
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="the reference is not on this machine (GPU box)")
 @pytest.mark.parametrize("d", [2, 3])
 def test_reference_dataloader_reads_our_file(tmp_path, d):
     want = _write_with_build(str(tmp_path), d, n_t=21)
-    out = os.path.join(str(tmp_path), "seen.npz")
-    _judge("load", tmp_path, "mine.h5", out)
-    seen = np.load(out)
+    seen = np.load(os.path.join(JUDGED, f"load_{d}d.npz"))
+    assert file_digest(os.path.join(str(tmp_path), "mine.h5")) == str(seen["file_digest"])     # the file the reference read
     assert np.array_equal(seen["vertices"], want["centers"]) and np.array_equal(seen["nodes"], want["nodes"])
     assert np.array_equal(seen["faces"], want["faces"]) and seen["faces"].dtype == np.int32
     assert np.array_equal(seen["levels"], want["levels"][:, 0]) and np.array_equal(seen["metric"], want["metric"])
@@ -252,10 +259,7 @@ def test_reference_dataloader_reads_our_file(tmp_path, d):
     assert np.array_equal(ld.weights.numpy(), seen["weights"]) and np.array_equal(ld.levels.numpy(), seen["levels"])
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="the reference is not on this machine (GPU box)")
-@pytest.mark.parametrize("d,with_data,with_const,mixed", [(2, True, True, 0), (3, True, True, 0), (3, False, True, 0),
-                                                          (2, True, False, 0), (2, False, False, 0), (3, True, True, 1),
-                                                          (2, False, True, 1)])
+@pytest.mark.parametrize("d,with_data,with_const,mixed", XDMF_PARAMS)
 def test_reference_xdmf_writer_agrees_on_our_file(tmp_path, d, with_data, with_const, mixed):
     """both XDMF writers describe the same file (temporal collection / single grid, with and without constants, Mixed):
     byte-identical text"""
@@ -263,26 +267,23 @@ def test_reference_xdmf_writer_agrees_on_our_file(tmp_path, d, with_data, with_c
     _write_with_build(str(tmp_path), d, n_t=12, with_data=with_data, with_const=with_const, seed=d)
     XDMFWriter(str(tmp_path), "mine.h5", mixed=bool(mixed)).write_xdmf()
     mine = open(os.path.join(str(tmp_path), "mine.xdmf")).read()
-    os.remove(os.path.join(str(tmp_path), "mine.xdmf"))
-    _judge("xdmf", tmp_path, "mine.h5", mixed)
-    theirs = open(os.path.join(str(tmp_path), "mine.xdmf")).read()
-    assert mine == theirs
+    judged = json.load(open(os.path.join(JUDGED, "xdmf.json")))[f"{d}-{with_data}-{with_const}-{mixed}"]
+    assert file_digest(os.path.join(str(tmp_path), "mine.h5")) == judged["file_digest"]         # the file the reference described
+    assert mine == judged["xdmf"]
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="the reference is not on this machine (GPU box)")
 def test_datawriter_script_equals_the_reference_datawriter(tmp_path):
     """``data.Datawriter`` driven directly, the way a user's script does (inputs.datawriter_script: write_grid through a loader,
     plain field names that get their ``_center`` / ``_vertices`` suffix, int / float / missing time steps, a duplicate, constants,
     XDMF): the reference's class (own process, h5py = the stand-in) and this package's write the same file -- same datasets in the
     same order, same shapes, dtypes and VALUES (nothing is computed here: bit-identical), byte-identical XDMF"""
+    import pathlib
     import shutil
     from inputs import datawriter_script
     from sparsespatialsampling_amd.data import Dataloader, Datawriter
-    theirs, mine = tmp_path / "theirs", tmp_path / "mine"
-    for d in (theirs, mine):
-        d.mkdir()
-        shutil.copy(os.path.join(GOLDEN, "s_cube_test_dataset.h5"), d / "src.h5")
-    _judge("write", theirs, "src.h5", "out.h5")
+    theirs, mine = pathlib.Path(JUDGED, "datawriter"), tmp_path / "mine"
+    mine.mkdir()
+    shutil.copy(os.path.join(GOLDEN, "s_cube_test_dataset.h5"), mine / "src.h5")
     datawriter_script(Dataloader, Datawriter, str(mine), "src.h5", "out.h5")
     a, b = inventory(str(mine / "out.h5")), inventory(str(theirs / "out.h5"))
     assert [p for p, _ in a] == [p for p, _ in b]
@@ -292,16 +293,15 @@ def test_datawriter_script_equals_the_reference_datawriter(tmp_path):
     assert open(mine / "out.xdmf").read() == open(theirs / "out.xdmf").read()
 
 
-def fuzz_export_against_reference(directory, seed0, n):
+def fuzz_export_against_reference(directory, seed0, n, ref_dir=os.path.join(JUDGED, "fuzz_export")):
     """n randomly drawn exports (inputs.random_export_case: dimension, cloud, batch cuts, vertices, one file per field, append, kind
-    of write times, scalar as [N, T]) run by the REAL reference in its own process -- grid generation included -- and by this
-    package's ExportData (host logic on the oracle-backed device stand-ins) on the reference's grid; returns the number compared"""
+    of write times, scalar as [N, T]) as the REAL reference wrote them -- grid generation included -- in `ref_dir` (one sub-directory
+    per seed: tests/golden/ref_judge.py fuzz_export) and by this package's ExportData (host logic on the oracle-backed device
+    stand-ins) on the reference's grid; returns the number compared"""
     import sparsespatialsampling_amd.export as export
     from inputs import random_export_case, random_export_cloud, run_random_export
     from sparsespatialsampling_amd import geometry
-    ref_dir, my_dir = os.path.join(directory, "ref"), os.path.join(directory, "mine")
-    os.makedirs(ref_dir)
-    _judge("fuzz_export", ref_dir, seed0, n)
+    my_dir = os.path.join(directory, "mine")
     saved, export.hipops = export.hipops, _cpu_ops()
     try:
         for seed in range(seed0, seed0 + n):
@@ -328,7 +328,6 @@ def fuzz_export_against_reference(directory, seed0, n):
     return n
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="the reference is not on this machine (GPU box)")
 def test_random_exports_equal_the_reference(tmp_path):
     assert fuzz_export_against_reference(str(tmp_path), 0, 6) == 6
 
