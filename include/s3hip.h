@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 6
+#define S3_ABI_VERSION 7
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -291,9 +291,6 @@ int s3_yard_stream(const void *d_src, void *d_dst, int64_t src_bytes, int64_t ds
                    int nontemporal, s3_stream stream, int64_t *h_bytes_read, int64_t *h_bytes_written);
 int s3_yard_plan_loads(s3_interp_plan *plan, const void *d_table, int64_t n_table_rows, int64_t row_bytes, int64_t stride_bytes,
                        int variant, s3_stream stream, int64_t *h_staged_bytes);
-/* re-read the S3_* environment switches of the planned launches (they are parsed once, at the first launch; A/B tools that
- * flip them inside one process call this after every change) */
-int s3_debug_reload_env(void);
 
 
 /* ---- device-side bookkeeping of the KNN cache (replaces torch.unique / fancy indexing on the a16 path) ----------

@@ -22,17 +22,9 @@
 // HBM/L2 traffic per tile-chunk drops from n_cells*k segments to n_distinct segments (2.5-3x fewer on the cylinder3D
 // workload), which moves the kernel from the Infinity-Cache gather bound towards the HBM bound.
 #include "common.h"
-#ifdef S3_PROBE_STAMPS
-__device__ long long s3_probe_stamps[1024 * 4 * 8];
-#define S3_STAMP(V) const long long V = __builtin_amdgcn_s_memrealtime();
-#else
-#define S3_STAMP(V)
-#endif
 #include "plan_build.h"
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <exception>
 #include <type_traits>
 #include <vector>
@@ -58,10 +50,7 @@ namespace s3 {
 
 constexpr int PL_SEG = 128;        // bytes of one row staged per chunk
 constexpr int PL_NP = 16;          // staging passes of (tile cells)/2 rows -> at most 8 * (tile cells) distinct rows
-#ifndef S3_PL_LP
-#define S3_PL_LP 8
-#endif
-constexpr int PL_LP = S3_PL_LP;    // LDS row pitch of the persistent kernel in 16-byte vectors.  9 (144 bytes: the rows of the cells a
+constexpr int PL_LP = 8;           // LDS row pitch of the persistent kernel in 16-byte vectors.  9 (144 bytes: the rows of the cells a
                                    // wavefront accumulates together then start in different banks) was measured against 8 in
                                    // alternating processes on one box: 0.167 / 0.152 / 0.457 ms against 0.167 / 0.149 / 0.466 ms at
                                    // 25 / 32 / 128 snapshots -- the bank conflicts are not on the critical path
@@ -418,18 +407,13 @@ interp_planned_short_quad_kernel(const int32_t *__restrict__ perm, const int32_t
 }
 
 // Dispatch order of the chunk kernels (one workgroup per (tile, run of column chunks); a 1-D grid, workgroup b on XCD b % 8).
-// XCD x owns the x-th eighth of the Hilbert-ordered tiles; its share is walked in BRICKS of `brick` consecutive tiles, and inside
-// a brick run-major: all tiles of the brick for chunk run 0, then for run 1, ... -- the workgroups resident on an XCD at the same
-// time then stage the same columns of rows that neighbouring tiles share (the halo) within a few steps of each other.
-// brick >= tiles_per_xcd: run-major over the whole share (the order of a 2-D grid); n_split = 1: tile order.
-__device__ __forceinline__ void brick_map(int64_t b, int64_t tiles_per_xcd, int brick, int n_split, int64_t &tile, int &run) {
+// XCD x owns the x-th eighth of the Hilbert-ordered tiles and walks its share run-major: all its tiles for chunk run 0, then for
+// run 1, ... (the order of a 2-D grid) -- the workgroups resident on an XCD at the same time then stage the same columns of rows
+// that neighbouring tiles share (the halo) within a few steps of each other.  One run per tile: tile order.
+__device__ __forceinline__ void run_map(int64_t b, int64_t tiles_per_xcd, int64_t &tile, int &run) {
     const int64_t i = b >> 3;
-    const int64_t per = (int64_t)brick * n_split;
-    const int64_t bk = i / per, rem = i - bk * per;
-    const int64_t left = tiles_per_xcd - bk * brick;
-    const int64_t bl = left < brick ? left : (int64_t)brick;
-    run = (int)(rem / bl);
-    tile = (b & 7) * tiles_per_xcd + bk * brick + (rem - (int64_t)run * bl);
+    run = (int)(i / tiles_per_xcd);
+    tile = (b & 7) * tiles_per_xcd + (i - (int64_t)run * tiles_per_xcd);
 }
 
 // The same with a finer grain at the END of every XCD's share: the last `tail` tiles are cut into `tail_split` runs of column
@@ -459,7 +443,7 @@ interp_planned_kernel(const int32_t *__restrict__ perm, const int32_t *__restric
                       const int32_t *__restrict__ tile_row_begin, const int32_t *__restrict__ rows,
                       const uint16_t *__restrict__ loc, const double *__restrict__ w /*plan order*/, int k, int ucap,
                       const T *__restrict__ data, int64_t row_len, int64_t in_stride, double *__restrict__ out,
-                      int64_t n_tiles, int64_t tiles_per_xcd, int chunks_per_block, int n_chunks, int brick, int n_split, int tail, int tail_split) {
+                      int64_t n_tiles, int64_t tiles_per_xcd, int chunks_per_block, int n_chunks, int tail, int tail_split) {
     using V = typename Vec16<T>::type;
     constexpr int EPV = Vec16<T>::N;                 // elements per 16-byte vector
     constexpr int EPC = PL_SEG / (int)sizeof(T);     // elements per chunk
@@ -475,7 +459,7 @@ interp_planned_kernel(const int32_t *__restrict__ perm, const int32_t *__restric
     if (tail > 0) {
         tail_map(blockIdx.x, tiles_per_xcd, tail, tail_split, n_chunks, tile, chunk0, chunk1);
     } else {
-        brick_map(blockIdx.x, tiles_per_xcd, brick, n_split, tile, run);     // XCD-aware (speed only)
+        run_map(blockIdx.x, tiles_per_xcd, tile, run);       // XCD-aware (speed only)
         chunk0 = run * chunks_per_block;
         chunk1 = min(n_chunks, chunk0 + chunks_per_block);
     }
@@ -487,7 +471,6 @@ interp_planned_kernel(const int32_t *__restrict__ perm, const int32_t *__restric
     const int r_begin = tile_row_begin[tile], n_r = tile_row_begin[tile + 1] - r_begin;
     const bool even_rows = (row_len & 1) == 0;                   // output rows 16-byte aligned -> double2 stores
 
-    // the tile's weights and LDS row positions, [neighbour][cell] so that a wavefront reads consecutive words
     // the tile's weights and LDS row positions, [neighbour][cell] so that a wavefront reads consecutive words
     stage_tile_tables(w + (int64_t)c_begin * k, loc + (int64_t)c_begin * k, n_c * k, s_w, s_loc, BLOCK);
 
@@ -592,13 +575,13 @@ __device__ __forceinline__ float4 select16(bool c, const float4 &a, const float4
 __device__ __forceinline__ double2 select16(bool c, const double2 &a, const double2 &b) {
     return make_double2(c ? a.x : b.x, c ? a.y : b.y);
 }
-template <typename T, int HOLD>      // HOLD: 0 every step writes its own 256 bytes (default); 1 whole-line output stores (below)
+template <typename T>
 __global__ void __launch_bounds__(256, 2)
 interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__restrict__ tile_cell_begin,
                             const int32_t *__restrict__ tile_row_begin, const int32_t *__restrict__ rows,
                             const uint16_t *__restrict__ loc, const double *__restrict__ w /*plan order*/, int k, int ucap,
                             const T *__restrict__ data, int64_t row_len, int64_t in_stride, double *__restrict__ out,
-                            int64_t n_tiles, int64_t tiles_per_xcd, int chunks_per_block, int n_chunks, int brick, int n_split, int tail, int tail_split) {
+                            int64_t n_tiles, int64_t tiles_per_xcd, int chunks_per_block, int n_chunks, int tail, int tail_split) {
     using V = typename Vec16<T>::type;
     constexpr int TC = 64;
     constexpr int EPV = Vec16<T>::N;
@@ -615,7 +598,7 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
     if (tail > 0) {
         tail_map(blockIdx.x, tiles_per_xcd, tail, tail_split, n_chunks, tile, chunk0, chunk1);
     } else {
-        brick_map(blockIdx.x, tiles_per_xcd, brick, n_split, tile, run);     // XCD-aware (speed only)
+        run_map(blockIdx.x, tiles_per_xcd, tile, run);       // XCD-aware (speed only)
         chunk0 = run * chunks_per_block;
         chunk1 = min(n_chunks, chunk0 + chunks_per_block);
     }
@@ -635,6 +618,32 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
     const bool has_cell = cl < n_c;
     const int64_t cell = has_cell ? perm[c_begin + cl] : 0;
 
+    // (defined here, ahead of the staging registers: defined behind them, the fp32 build paired a row's line loads as
+    // {y, z} in misaligned registers and copied them out right after the load -- a wait for a line just requested, every step)
+    auto accumulate = [&](int chunk) {
+        if (!has_cell) return;
+        const int64_t col0 = (int64_t)chunk * EPC;
+        double acc0[EPV], acc1[EPV];
+#pragma unroll
+        for (int i = 0; i < EPV; ++i) acc0[i] = acc1[i] = 0.0;
+#pragma unroll 4
+        for (int m = 0; m < k; ++m) {
+            const int pos = s_loc[m * TC + cl];
+            const double wm = s_w[m * TC + cl];
+            const V a = s_data[pos * 8 + v0];
+            const V c = s_data[pos * 8 + v0 + 4];
+            const T *ae = reinterpret_cast<const T *>(&a);
+            const T *ce = reinterpret_cast<const T *>(&c);
+#pragma unroll
+            for (int i = 0; i < EPV; ++i) {
+                acc0[i] = fma(wm, (double)ae[i], acc0[i]);
+                acc1[i] = fma(wm, (double)ce[i], acc1[i]);
+            }
+        }
+        double *o = out + cell * row_len + col0;
+        store_piece<EPV>(o + v0 * EPV, acc0, row_len - col0 - (int64_t)v0 * EPV, even_rows);
+        store_piece<EPV>(o + (v0 + 4) * EPV, acc1, row_len - col0 - (int64_t)(v0 + 4) * EPV, even_rows);
+    };
 
     const int srow = threadIdx.x >> 3, svec = threadIdx.x & 7;
     const uintptr_t base = reinterpret_cast<uintptr_t>(data);
@@ -697,87 +706,31 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
 #define S3H_STORE2(P, OLD, NEW) *reinterpret_cast<V *>(lds_raw_bytes + lds##P) = select16(old##P, OLD, NEW);
 #define S3H_STORE_AB(P) S3H_STORE2(P, preA##P, preB##P)
 #define S3H_STORE_BA(P) S3H_STORE2(P, preB##P, preA##P)
-#define S3H_STORES_DONE()
 
-    // Output rows of 8 * row_len bytes start 64 bytes into a 128-byte line whenever row_len is an odd multiple of 8 (1000 snapshots:
-    // 8000-byte rows, every other cell): the 256 bytes a cell writes per step then end in HALF a line whose other half follows a
-    // step (7 us) later -- the L2 has turned over by then and the line goes out as two partial writes (WRITE_SIZE 7 % over the
-    // output's size).  Such a cell holds its last 64 bytes (blocks 6 and 7 of the chunk: the second vector of its lanes
-    // 2 and 3) back for one step, so that every step writes the whole aligned lines [c * 256 - 64, c * 256 + 192) of the row.
-    bool defer = false;
-    if constexpr (std::is_same<T, float>::value && HOLD != 0)
-        defer = has_cell && even_rows && v0 >= 2 && (reinterpret_cast<uintptr_t>(out + cell * row_len) & 127) == 64;
-    double held0 = 0.0, held1 = 0.0, held2 = 0.0, held3 = 0.0;      // (named: a loop-carried local array ends up in scratch memory)
-
-    auto accumulate = [&](int chunk) {
-        if (!has_cell) return;
-        const int64_t col0 = (int64_t)chunk * EPC;
-        double acc0[EPV], acc1[EPV];
-#pragma unroll
-        for (int i = 0; i < EPV; ++i) acc0[i] = acc1[i] = 0.0;
-#pragma unroll 4
-        for (int m = 0; m < k; ++m) {
-            const int pos = s_loc[m * TC + cl];
-            const double wm = s_w[m * TC + cl];
-            const V a = s_data[pos * 8 + v0];
-            const V c = s_data[pos * 8 + v0 + 4];
-            const T *ae = reinterpret_cast<const T *>(&a);
-            const T *ce = reinterpret_cast<const T *>(&c);
-#pragma unroll
-            for (int i = 0; i < EPV; ++i) {
-                acc0[i] = fma(wm, (double)ae[i], acc0[i]);
-                acc1[i] = fma(wm, (double)ce[i], acc1[i]);
-            }
-        }
-        double *o = out + cell * row_len + col0;
-        store_piece<EPV>(o + v0 * EPV, acc0, row_len - col0 - (int64_t)v0 * EPV, even_rows);
-        if (EPV == 4 && HOLD == 1 && defer) {
-            // (the chunk before this one is never the row's last: its piece is whole)
-            if constexpr (EPV == 4) {
-                if (chunk > chunk0) {
-                    double *h = o - EPC + (v0 + 4) * EPV;
-                    *reinterpret_cast<double2 *>(h) = make_double2(held0, held1);
-                    *reinterpret_cast<double2 *>(h + 2) = make_double2(held2, held3);
-                }
-                held0 = acc1[0], held1 = acc1[1], held2 = acc1[2], held3 = acc1[3];
-            }
-        } else {
-            store_piece<EPV>(o + (v0 + 4) * EPV, acc1, row_len - col0 - (int64_t)(v0 + 4) * EPV, even_rows);
-        }
-    };
 
     // Built, measured and NOT kept (r5): chunk phases tied to a chip-wide clock (time cut into slots of the 100-MHz counter, slot n
     // belongs to chunk n mod n_chunks on every workgroup, the loads of a step issued no earlier than its slot begins, a tile sweeping
     // [c_start, n) and then [0, c_start)).  Tiles that share rows then ask for the same lines within the few microseconds the L2 keeps
     // them: FETCH_SIZE -11.6 % with 10-us slots, -6.3 % at 6.0 us, -3.7 % at 5.4 us (a step takes 5.8 us on its own) -- but the launch
     // took 4.07 / 3.86 ms against 3.65: in lock-step all workgroups load at once and compute at once, and the overlap between
-    // workgroups that the memory system lives on is gone.  (tools/ab_order.py, tools/pmc_order.sh; HISTORY 5.1b.)
+    // workgroups that the memory system lives on is gone.  (HISTORY 5.1b.)
     if (chunk0 < chunk1) {
         S3H_ISSUE(A, chunk0, 0);
         S3H_ISSUE(B, chunk0 + 1, 1);
     }
     for (int chunk = chunk0; chunk < chunk1; chunk += 2) {
         S3_REP16(S3H_STORE_AB)
-        S3H_STORES_DONE();
         __syncthreads();
         if (chunk + 1 < chunk1) S3H_ISSUE(A, chunk + 2, 2);
         accumulate(chunk);
         __syncthreads();
         if (chunk + 1 >= chunk1) break;
         S3_REP16(S3H_STORE_BA)
-        S3H_STORES_DONE();
         __syncthreads();
         if (chunk + 2 < chunk1) S3H_ISSUE(B, chunk + 3, 3);
         accumulate(chunk + 1);
         __syncthreads();
         S3_REP16(S3H_ADVANCE)
-    }
-    if (defer && chunk1 > chunk0) {              // the held piece of the run's last chunk (ragged tails: nothing beyond the row)
-        const int64_t col0 = (int64_t)(chunk1 - 1) * EPC;
-        if constexpr (EPV == 4) {
-            const double held[EPV] = {held0, held1, held2, held3};
-            store_piece<EPV>(out + cell * row_len + col0 + (v0 + 4) * EPV, held, row_len - col0 - (int64_t)(v0 + 4) * EPV, even_rows);
-        }
     }
 #undef S3H_ADVANCE
 #undef S3H_DECL
@@ -791,7 +744,6 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
 #undef S3H_STORE2
 #undef S3H_STORE_AB
 #undef S3H_STORE_BA
-#undef S3H_STORES_DONE
 }
 
 // Rows that start on element boundaries only (a dense [N, n_comp * T] batch read where it lies: 25 fp32 snapshots make
@@ -817,7 +769,7 @@ struct StreamLayoutNarrow    { static constexpr int CHUNK_VECS = 4, LP = 4, VOFF
 //   * row segments of step s+1: sixteen named registers per lane, issued BETWEEN the neighbour pairs of step s's accumulate phase
 //     (r4; before: all sixteen right after the barrier.  A CU accepts only so many line requests at a time: the sixteen gathers of a
 //     lane took 2.4-3.7 us to issue, during which the wavefront -- in order -- could not start its conversions and FMAs; s_memrealtime
-//     stamps, tools/stream_phases.sh.  Spread over the phase the requests drain while the wavefront computes);
+//     stamps, HISTORY 5.2b.  Spread over the phase the requests drain while the wavefront computes);
 //   * weights / positions of the next tile: in REGISTERS, shared by the four lanes of a cell (each lane loads every fourth
 //     entry of its cell, the DPP quad broadcasts them when the neighbour's turn comes) -- LDS holds row data only, so there
 //     is nothing to double-buffer there;
@@ -901,7 +853,7 @@ __device__ __forceinline__ void stream_fma_row(double wm, const double2 &a, cons
 // reads or accumulates them
 // `issue(slot)`: the row-segment loads of the NEXT step that belong to neighbour pair `slot` -- the sixteen loads of a lane are spread
 // over the pairs of the accumulate phase instead of standing in front of it: a CU accepts only so many line requests at a time, the
-// issue of sixteen gathers per lane blocks for 2-4 us (s_memrealtime stamps, tools/stream_phases.sh) and the wavefront, in-order,
+// issue of sixteen gathers per lane blocks for 2-4 us (s_memrealtime stamps, HISTORY 5.2b) and the wavefront, in-order,
 // cannot start its conversions and FMAs behind it; between the pairs the requests drain while the wavefront computes.
 template <int M, int K, bool BOTH, typename T, typename LAY, typename ISSUE>
 __device__ __forceinline__ void stream_accumulate(const double (&wq)[(K + 3) / 4], const int (&pq)[(K + 3) / 4],
@@ -1051,9 +1003,6 @@ interp_planned_stream_kernel(const int32_t *__restrict__ perm, const int32_t *__
 #pragma unroll
     for (int i = 0; i < 8; ++i) *reinterpret_cast<volatile double *>(dump_lane) = 0.0;
 
-#ifdef S3_PROBE_STAMPS
-    long long pr_sum[7] = {0, 0, 0, 0, 0, 0, 0};
-#endif
     for (int j = 0; j < n_my; ++j) {
         // the tile whose steps are accumulated now: its tables arrived behind its first row segments
 #pragma unroll
@@ -1070,15 +1019,12 @@ interp_planned_stream_kernel(const int32_t *__restrict__ perm, const int32_t *__
             const bool enter_next = last_chunk && j + 1 < n_my;      // the issue pointer moves on to this workgroup's next tile
             const int64_t store_c0_ = (int64_t)c * EPC;
             (void)store_c0_;
-            S3_STAMP(ts0)
             S3_REP16(S3S_STORE)
             if (enter_next) {
                 s_ids[tid] = ida;
                 s_ids[BLOCK + tid] = idb;
             }
-            S3_STAMP(ts1)
             __syncthreads();
-            S3_STAMP(ts2)
             // ONE issue site for the row segments (two would look to the compiler as if the second could overwrite registers
             // the first has loads pending for: it then waits for vmcnt(0), i.e. for the previous step's stores)
             if (enter_next) {                        // (older than the row segments: waiting for a table never waits for a segment)
@@ -1102,7 +1048,6 @@ interp_planned_stream_kernel(const int32_t *__restrict__ perm, const int32_t *__
                 constexpr int S = decltype(slot)::value, NS = sizeof(T) == 4 ? (K + 1) / 2 : 1;
                 S3_REP16(S3S_LOAD_IF)
             };
-            S3_STAMP(ts3)
             const int64_t col0 = (int64_t)c * EPC;
             double acc0[EPV], acc1[EPV];
 #pragma unroll
@@ -1120,7 +1065,6 @@ interp_planned_stream_kernel(const int32_t *__restrict__ perm, const int32_t *__
                 stream_accumulate<0, K, false, T, LAY>(wq, pq, s_data, v0, buf_a, buf_b, acc0, acc1, issue);
             }
             __builtin_amdgcn_sched_barrier(0);
-            S3_STAMP(ts4)
             // the same number of stores on every path: what must not be written goes to this lane's dump slot.  Pairs of
             // doubles; rows of odd length start on 8-byte boundaries only (element-aligned 16-byte stores) and end in a
             // single element, which one lane of the cell stores separately.
@@ -1159,21 +1103,9 @@ interp_planned_stream_kernel(const int32_t *__restrict__ perm, const int32_t *__
                 double *pt = live && mine ? orow + t : dump_lane;
                 *pt = tv;
             }
-            S3_STAMP(ts5)
             __syncthreads();
-#ifdef S3_PROBE_STAMPS
-            {
-                const long long ts6 = __builtin_amdgcn_s_memrealtime();
-                pr_sum[0] += ts1 - ts0; pr_sum[1] += ts2 - ts1; pr_sum[2] += ts3 - ts2; pr_sum[3] += ts4 - ts3; pr_sum[4] += ts5 - ts4; pr_sum[5] += ts6 - ts5;
-                pr_sum[6] += 1;
-            }
-#endif
         }
     }
-#ifdef S3_PROBE_STAMPS
-    if ((tid & 63) == 0 && blockIdx.x < 1024)
-        for (int i = 0; i < 8; ++i) s3_probe_stamps[(blockIdx.x * 4 + (tid >> 6)) * 8 + i] = i < 7 ? pr_sum[i] : 0;
-#endif
 #undef S3S_DECL
 #undef S3S_RID
 #undef S3S_LOAD
@@ -1184,61 +1116,16 @@ interp_planned_stream_kernel(const int32_t *__restrict__ perm, const int32_t *__
 
 #undef S3_REP16
 
-// distinct rows a tile of `tc` cells may hold: what is left of the LDS budget (80 KiB -> two 256-thread workgroups per CU
-// for tc = 64; 160 KiB -> one 512-thread workgroup per CU for tc = 128) after the tile's weights and positions
-// rows of at most this many 16-byte vectors take the short-row kernel (S3_SHORT_ROW_VECS overrides, for A/B runs).
+// rows of at most this many 16-byte vectors take the short-row kernels.
 // Measured on MI355X, cylinder3D grid (461 130 cells, k = 26, fp32): 16 snapshots (4 vectors) 0.139 ms short / 0.162 ms
 // chunk kernel / 0.170 ms direct gather; from 25 snapshots on the chunk kernel is faster (0.189 vs 0.282 ms)
-static int short_row_vecs() {
-    static const int v = [] {
-        const char *e = getenv("S3_SHORT_ROW_VECS");
-        return e ? atoi(e) : 4;
-    }();
-    return v;
-}
+constexpr int SHORT_ROW_VECS = 4;
 
 // fewest workgroups a launch of the chunk kernel should have before the column chunks are split over blockIdx.y
-// (S3_PLAN_MIN_BLOCKS overrides, for A/B runs)
-// The S3_* switches of the planned launches (A/B runs, tests) are parsed ONCE, at the first launch: getenv on every launch raced with
-// the interpreter's putenv from other threads.  A tool that flips a switch inside a process calls s3_debug_reload_env()
-// afterwards (hipops.reload_env()) -- not while another thread launches.
-struct LaunchSwitches {
-    int64_t min_blocks = 2048, stream_min_tiles = 64;
-    int stream_max_chunks = 24, inplace_shift = 1, shift_min_chunks = 6;
-    int short_stream = -1;                      // -1 unset (decided by the table's size), 0 never, 1 always
-    bool short_no_quad = false, short_lds_weights = false;
-    int plan_split = 0, plan_brick = 0;         // 0 unset
-    bool tail_given = false;
-    int tail = 32, tail_split = 4;
-    int out_hold = 0;
-};
-static LaunchSwitches parse_switches() {
-    LaunchSwitches w;
-    if (const char *e = getenv("S3_PLAN_MIN_BLOCKS")) w.min_blocks = atoll(e);
-    if (const char *e = getenv("S3_STREAM_MIN_TILES")) w.stream_min_tiles = atoll(e);
-    if (const char *e = getenv("S3_STREAM_MAX_CHUNKS")) w.stream_max_chunks = atoi(e);
-    if (const char *e = getenv("S3_INPLACE_SHIFT")) w.inplace_shift = atoi(e);
-    if (const char *e = getenv("S3_SHIFT_MIN_CHUNKS")) w.shift_min_chunks = atoi(e);
-    if (const char *e = getenv("S3_SHORT_STREAM")) w.short_stream = e[0] == '1' ? 1 : 0;
-    w.short_no_quad = getenv("S3_SHORT_NO_QUAD") != nullptr;
-    w.short_lds_weights = getenv("S3_SHORT_LDS_WEIGHTS") != nullptr;
-    if (const char *e = getenv("S3_PLAN_SPLIT")) w.plan_split = atoi(e) < 1 ? 1 : atoi(e);
-    if (const char *e = getenv("S3_PLAN_BRICK")) w.plan_brick = atoi(e) < 1 ? 1 : atoi(e);
-    if (const char *e = getenv("S3_PLAN_TAIL")) {
-        w.tail_given = true;
-        w.tail = atoi(e);
-        const char *x = strchr(e, 'x');
-        w.tail_split = x ? atoi(x + 1) : 4;
-    }
-    if (const char *e = getenv("S3_OUT_HOLD")) w.out_hold = atoi(e);
-    return w;
-}
-static LaunchSwitches &switches() {
-    static LaunchSwitches w = parse_switches();
-    return w;
-}
-static int64_t min_blocks() { return switches().min_blocks; }
+constexpr int64_t PLAN_MIN_BLOCKS = 2048;
 
+// distinct rows a tile of `tc` cells may hold: what is left of the LDS budget (80 KiB -> two 256-thread workgroups per CU
+// for tc = 64; 160 KiB -> one 512-thread workgroup per CU for tc = 128) after the tile's weights and positions
 static int plan_ucap(int k, int tc) {
     const int budget = (tc == 128 ? 160 : 80) * 1024;
     int u = (budget - k * tc * (int)(sizeof(double) + sizeof(uint16_t))) / PL_SEG;
@@ -1251,22 +1138,20 @@ static int plan_ucap(int k, int tc) {
 
 using namespace s3;
 
-// the persistent kernel (interp_planned_stream_kernel) takes batches of up to this many 128-byte column chunks per row
-// (S3_STREAM_MAX_CHUNKS overrides; 0 switches it off) on plans with at least S3_STREAM_MIN_TILES tiles.  24 (r4; 8 before the
-// segment loads were spread over its accumulate phase): rows on the line grid, cylinder3D plan, one process -- 288 / 320 / 384 /
-// 512 / 768 snapshots 1.049 / 1.046 / 1.259 / 1.767 / 2.478 ms against 1.117 / 1.090 / 1.307 / 1.841 / 2.608 with the chunk kernel;
-// 1000 snapshots (32 chunks) 3.689 against 3.529: the long sweeps stay with the chunk kernel's two chunks of prefetch
-static int stream_max_chunks() { return s3::switches().stream_max_chunks; }
-static int64_t stream_min_tiles() { return s3::switches().stream_min_tiles; }
-static int inplace_shift() { return s3::switches().inplace_shift; }   // 0: never (A/B runs), 1: rows off the 128-byte grid (default), 2: always (A/B runs)
+// the persistent kernel (interp_planned_stream_kernel) takes batches of up to this many 128-byte column chunks per row on plans
+// of at least STREAM_MIN_TILES tiles.  24 (r4; 8 before the segment loads were spread over its accumulate phase): rows on the
+// line grid, cylinder3D plan, one process -- 288 / 320 / 384 / 512 / 768 snapshots 1.049 / 1.046 / 1.259 / 1.767 / 2.478 ms against
+// 1.117 / 1.090 / 1.307 / 1.841 / 2.608 with the chunk kernel; 1000 snapshots (32 chunks) 3.689 against 3.529: the long sweeps stay
+// with the chunk kernel's two chunks of prefetch
+constexpr int STREAM_MAX_CHUNKS = 24;
+constexpr int64_t STREAM_MIN_TILES = 64;
 // rows OFF the line grid of at least this many chunks take the shift kernel (whole aligned lines), shorter ones the persistent
 // kernel with straddling segments.  6 (r4; 3 before): dense rows of 68 / 100 / 136 / 200 / 300 / 600 snapshots (3 / 4 / 5 / 7 / 10 /
 // 19 chunks), one process: shift 0.409 / 0.535 / 0.618 / 0.842 / 1.214 / 2.176 ms, persistent 0.372 / 0.535 / 0.605 / 0.862 / 1.362 / 2.531
-static int shift_min_chunks() { return s3::switches().shift_min_chunks; }
+constexpr int SHIFT_MIN_CHUNKS = 6;
+// workgroups of the persistent kernel
 static int stream_workgroups() {
     static const int v = [] {
-        const char *e = getenv("S3_STREAM_WORKGROUPS");
-        if (e) return atoi(e);
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         return 2 * cus;                                   // LDS: two workgroups per CU
@@ -1291,34 +1176,18 @@ static int plan_schedule(s3_interp_plan *p, hipStream_t st) {
     const int slots = wgs / 8;
     const size_t per_xcd = (nt + 7) / 8;
     std::vector<std::vector<int32_t>> lists((size_t)wgs);
-    std::vector<double> busy((size_t)slots);
-    // Default: plain round robin -- the workgroups of an XCD then work on adjacent tiles at the same time and find most of a
-    // tile's halo in the XCD's L2.  S3_STREAM_SCHEDULE=cost: each tile to the workgroup expected to be free first (list
-    // scheduling with a byte-count cost model).  Measured on MI355X, cylinder3D grid, interleaved in one process
-    // (tools/ab_plan.py): round robin 0.158 / 0.151 / 0.454 ms at 25 / 32 / 128 snapshots, cost model 0.162 / 0.153 / 0.476 --
-    // the balance it buys is worth less than the locality it loses.
-    const char *mode = getenv("S3_STREAM_SCHEDULE");
-    const bool round_robin = !(mode && mode[0] == 'c');
+    // Plain round robin -- the workgroups of an XCD then work on adjacent tiles at the same time and find most of a tile's halo in
+    // the XCD's L2.  Each tile to the workgroup expected to be free first (list scheduling with a byte-count cost model) was
+    // measured on MI355X, cylinder3D grid, interleaved in one process (HISTORY 5.2b): round robin 0.158 / 0.151 / 0.454 ms at
+    // 25 / 32 / 128 snapshots, cost model 0.162 / 0.153 / 0.476 -- the balance it buys is worth less than the locality it loses.
     // (r5: balancing INSIDE a round -- the 64 tiles of a round, most expensive first, to the workgroups with the least work so far,
     // so that the rounds stay together in time -- measured too: 0.1344 / 0.1318 / 0.464 / 0.476 / 0.934 ms at 25 / 32 / 100 / 128 / 256
     // snapshots against 0.1317 / 0.1295 / 0.444 / 0.445 / 0.875 with plain round robin.  What round robin has is CORRELATION: workgroup
     // s always works on the tile next to workgroup s + 1's, neighbouring tiles cost about the same, so the two stay in phase and
     // share their halo through the L2; any reassignment breaks the pairs.)
-    auto cost_of = [&](size_t t) { return 128.0 * (rb[t + 1] - rb[t]) + (10.0 * p->k + 256.0) * (cb[t + 1] - cb[t]) + 4096.0; };
     for (int x = 0; x < 8; ++x) {
         const size_t lo = std::min(nt, x * per_xcd), hi = std::min(nt, lo + per_xcd);
-        std::fill(busy.begin(), busy.end(), 0.0);
-        for (size_t t = lo; t < hi; ++t) {
-            int best = 0;
-            if (round_robin) {
-                best = (int)((t - lo) % (size_t)slots);
-            } else {
-                for (int s = 1; s < slots; ++s)
-                    if (busy[s] < busy[best]) best = s;                 // (first of equals: the first `slots` tiles go out in order)
-            }
-            busy[best] += cost_of(t);
-            lists[(size_t)best * 8 + x].push_back((int32_t)t);
-        }
+        for (size_t t = lo; t < hi; ++t) lists[(t - lo) % (size_t)slots * 8 + x].push_back((int32_t)t);
     }
     std::vector<int32_t> begin((size_t)wgs + 1, 0), tiles;
     tiles.reserve(nt);
@@ -1420,37 +1289,30 @@ static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows
     constexpr int EPC = PL_SEG / (int)sizeof(T);
     constexpr int EPV = 16 / (int)sizeof(T);
     const int n_chunks = (int)((row_len + EPC - 1) / EPC);
+    const int vpr = (int)((row_len + EPV - 1) / EPV);           // 16-byte vectors per row
     const int64_t tiles_per_xcd = (p->n_tiles + 7) / 8;
     const int64_t gx = tiles_per_xcd * 8;
     S3_REQUIRE(gx < ((int64_t)1 << 31), "s3_interp_planned: too many tiles");
-    // rows off the 128-byte grid (a dense batch read where it lies) with three or more chunks are better off with whole aligned
-    // lines (interp_planned_shift_kernel, below) than with the persistent kernel's straddling segments: 800-byte rows 0.850
+    const bool stream_ok = stream_can_take(p) && p->n_tiles >= STREAM_MIN_TILES;
+    // rows off the 128-byte grid (a dense batch read where it lies) with SHIFT_MIN_CHUNKS or more chunks are better off with whole
+    // aligned lines (interp_planned_shift_kernel, below) than with the persistent kernel's straddling segments: 800-byte rows 0.850
     // against 0.906 ms, 400-byte rows 0.529 / 0.553, 272-byte rows 0.414 / 0.424 (cylinder3D grid, interleaved in one process,
-    // tools/ab_inplace.py; S3_SHIFT_MIN_CHUNKS overrides)
+    // HISTORY 5.1b)
     const bool off_line = reinterpret_cast<uintptr_t>(data) % PL_SEG != 0 || ((uint64_t)in_stride * sizeof(T)) % PL_SEG != 0;
-    const bool shift_ok = p->tc == 64 && (off_line ? inplace_shift() >= 1 : inplace_shift() >= 2);
-    if ((row_len + EPV - 1) / EPV > s3::short_row_vecs() && n_chunks <= stream_max_chunks() && stream_can_take(p) &&
-        p->n_tiles >= stream_min_tiles() && !(off_line && shift_ok && n_chunks >= shift_min_chunks()))
+    const bool shift = p->tc == 64 && off_line;
+    if (vpr > SHORT_ROW_VECS && n_chunks <= STREAM_MAX_CHUNKS && stream_ok && !(shift && n_chunks >= SHIFT_MIN_CHUNKS))
         return launch_stream<T, true>(p, rows, data, row_len, in_stride, out, st);
     // (r4) rows of two to four vectors (5 .. 16 fp32 snapshots): the persistent kernel in its narrow layout -- four lanes per row,
     // eight gathers per lane and step -- unless the table is a large one read in place.  Measured, one box each: cylinder3D, 16 / 12
     // snapshots, pitched copy 0.089 / 0.088 ms against 0.105 / 0.117 with the short-row kernels, read in place (320-MB table) 0.100 /
     // 0.116 against 0.112 / 0.121; box5e7 (10 M cells, 16 snapshots) pitched copy 1.745 against 1.786 ms, but its 3.2-GB table read in
     // place 2.363 against 2.208: there five short-lived workgroups per CU hide the page-table walks of a scattered table better
-    // than two persistent ones.  Rows of one vector stay with the short-row kernels (0.096 against 0.078 ms).  S3_SHORT_STREAM=0 / 1:
-    // never / always, for A/B runs.
-    {
-        const int vpr_ = (int)((row_len + EPV - 1) / EPV);
-        const int sw = s3::switches().short_stream;
-        const bool in_place = rows != p->rows;
-        const bool big_table = in_place && (uint64_t)n_rows * (uint64_t)in_stride * sizeof(T) > ((uint64_t)1 << 30);
-        const bool want = sw >= 0 ? sw == 1 : !big_table;
-        if (vpr_ >= 2 && vpr_ <= 4 && want && stream_can_take(p) && p->n_tiles >= stream_min_tiles())
-            return launch_stream<T, true, true>(p, rows, data, row_len, in_stride, out, st);
-    }
-    if ((row_len + EPV - 1) / EPV <= s3::short_row_vecs() && p->tc == 64) {
-        const int vpr = (int)((row_len + EPV - 1) / EPV);
-        if (vpr == 4 && p->ucap * vpr <= 256 * 8 && p->k <= 32 && !s3::switches().short_no_quad && !s3::switches().short_lds_weights) {
+    // than two persistent ones.  Rows of one vector stay with the short-row kernels (0.096 against 0.078 ms).
+    const bool big_table = rows != p->rows && (uint64_t)n_rows * (uint64_t)in_stride * sizeof(T) > ((uint64_t)1 << 30);
+    if (vpr >= 2 && vpr <= 4 && !big_table && stream_ok)
+        return launch_stream<T, true, true>(p, rows, data, row_len, in_stride, out, st);
+    if (vpr <= SHORT_ROW_VECS && p->tc == 64) {
+        if (vpr == 4 && p->ucap * vpr <= 256 * 8 && p->k <= 32) {
             // four vectors per row: the lanes of a cell are a DPP quad and share the loads of its weights / positions
             const size_t lds = (size_t)p->ucap * vpr * 16;
 #define S3_LAUNCH_SHORT_QUAD(KQ)                                                                                                 \
@@ -1467,7 +1329,7 @@ static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows
             S3_LAUNCH_CHECK();
             return S3_OK;
         }
-        if (vpr <= 4 && p->ucap * vpr <= 256 * 8 && p->k <= 32 && !s3::switches().short_lds_weights) {
+        if (vpr <= 4 && p->ucap * vpr <= 256 * 8 && p->k <= 32) {
             // one lane per (cell, vector) pair, weights in registers
             const size_t lds = (size_t)p->ucap * vpr * 16;
 #define S3_LAUNCH_SHORT_REG(KM)                                                                                                  \
@@ -1496,53 +1358,38 @@ static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows
         return S3_OK;
     }
     // The column chunks of a tile are split into runs over several workgroups when there are too few tiles to fill the chip
-    // (S3_PLAN_MIN_BLOCKS), or on request (S3_PLAN_SPLIT = runs per tile, S3_PLAN_BRICK = tiles per XCD and brick; brick_map above).
-    // One workgroup per tile over ALL chunks was fastest in round 1 (MI355X, cylinder3D workload: 3.7 ms vs 4.4 ms with 4 chunks per
-    // workgroup, runs in 2-D grid order)
+    // (PLAN_MIN_BLOCKS; run_map above).  One workgroup per tile over ALL chunks was fastest in round 1 (MI355X, cylinder3D workload:
+    // 3.7 ms vs 4.4 ms with 4 chunks per workgroup, runs in 2-D grid order)
     int gy = 1;
-    while (gx * gy < s3::min_blocks() && gy < n_chunks) gy *= 2;
-    const LaunchSwitches &sw_ = s3::switches();
-    if (sw_.plan_split > 0) gy = sw_.plan_split;
+    while (gx * gy < PLAN_MIN_BLOCKS && gy < n_chunks) gy *= 2;
     if (gy > n_chunks) gy = n_chunks;
-    if (gy < 1) gy = 1;
     const int chunks_per_block = (n_chunks + gy - 1) / gy;
     gy = (n_chunks + chunks_per_block - 1) / chunks_per_block;
-    int brick = (int)std::min<int64_t>(tiles_per_xcd, 1 << 30);
-    if (sw_.plan_brick > 0) brick = std::max(1, std::min(brick, sw_.plan_brick));
-    // a finer grain for the last tiles of every XCD's share (tail_map): only where a tile is swept by ONE workgroup and a launch
-    // has several rounds of tiles per slot to drain (S3_PLAN_TAIL="<tiles per XCD>x<runs>", 0 = off)
-    int tail = 0, tail_split = 1;
-    if (gy == 1 && (sw_.tail_given || (n_chunks >= 8 && tiles_per_xcd >= 4 * 64))) {
-        tail = 32, tail_split = 4;          // (MI355X, cylinder3D, interleaved in one process: off 3.768 ms, 64x4 3.749, 32x4 3.736, 128x4 3.789, 64x8 3.781)
-        if (sw_.tail_given) tail = sw_.tail, tail_split = sw_.tail_split;
-        if (tail > tiles_per_xcd) tail = (int)tiles_per_xcd;
-        if (tail_split > n_chunks) tail_split = n_chunks;
-        if (tail < 1 || tail_split < 2) tail = 0, tail_split = 1;
-    }
-    const int64_t n_wg = tail > 0 ? 8 * (tiles_per_xcd + (int64_t)tail * (tail_split - 1)) : gx * gy;
+    // a finer grain for the last TAIL_TILES tiles of every XCD's share, TAIL_RUNS runs each (tail_map): only where a tile is swept by
+    // ONE workgroup and a launch has several rounds of tiles per slot to drain -- which also keeps TAIL_TILES <= tiles_per_xcd and
+    // TAIL_RUNS <= n_chunks.  (MI355X, cylinder3D, interleaved in one process: off 3.768 ms, 64x4 3.749, 32x4 3.736, 128x4 3.789,
+    // 64x8 3.781)
+    constexpr int TAIL_TILES = 32, TAIL_RUNS = 4;
+    const bool use_tail = gy == 1 && n_chunks >= 8 && tiles_per_xcd >= 4 * 64;
+    const int tail = use_tail ? TAIL_TILES : 0, tail_split = use_tail ? TAIL_RUNS : 1;
+    const int64_t n_wg = use_tail ? 8 * (tiles_per_xcd + (int64_t)tail * (tail_split - 1)) : gx * gy;
     S3_REQUIRE(n_wg < ((int64_t)1 << 31), "s3_interp_planned: too many workgroups");
     const size_t lds = (size_t)p->ucap * PL_SEG + (size_t)p->k * p->tc * (sizeof(double) + sizeof(uint16_t));
     dim3 grid((unsigned)n_wg);
     // rows that do not start on 128-byte boundaries (a dense batch read where it lies): whole aligned lines per load, the
-    // per-row phase undone on the way into LDS (S3_INPLACE_SHIFT=0: the kernel below with straddling segments, for A/B runs)
-    if (shift_ok) {
-        // S3_OUT_HOLD=1: whole-line output stores (HOLD = 1 above).  They bring WRITE_SIZE down to the output's size (3.955 -> 3.690 GB
-        // per launch at 1000 snapshots, traffic 1.31 -> 1.29 x algorithmic) but cost the launch 0.2-0.9 % (3.564 against 3.531 ms,
-        // 3.488 / 3.456, 3.575 / 3.569 on three boxes, interleaved in one process): the counter tallies two partial write-backs of a
-        // line as more than the line, the DRAM bursts are the same, and the divergent store path is not free.  Off by default.
-        // (A form with ONE store sequence for all lanes behind selects: 3.588 ms -- worse than the branch.)
-        const int hold = sw_.out_hold;
-#define S3_LAUNCH_SHIFT(H)                                                                                                       \
-    do {                                                                                                                         \
-        auto kern = interp_planned_shift_kernel<T, H>;                                                                           \
-        S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        kern<<<grid, 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,        \
-                                     static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles, tiles_per_xcd,           \
-                                     chunks_per_block, n_chunks, brick, gy, tail, tail_split);                                   \
-    } while (0)
-        if (hold == 0 || !std::is_same<T, float>::value) S3_LAUNCH_SHIFT(0);
-        else S3_LAUNCH_SHIFT(1);
-#undef S3_LAUNCH_SHIFT
+    // per-row phase undone on the way into LDS.
+    // (r5) Whole-line output stores -- a cell whose output row starts 64 bytes into a line holds the last 64 bytes of a step back
+    // for one step -- were built and not kept.  They bring WRITE_SIZE down to the output's size (3.955 -> 3.690 GB per launch at
+    // 1000 snapshots, traffic 1.31 -> 1.29 x algorithmic) but cost the launch 0.2-0.9 % (3.564 against 3.531 ms, 3.488 / 3.456,
+    // 3.575 / 3.569 on three boxes, interleaved in one process): the counter tallies two partial write-backs of a line as more than
+    // the line, the DRAM bursts are the same, and the divergent store path is not free.  (A form with ONE store sequence for all
+    // lanes behind selects: 3.588 ms -- worse than the branch.)  HISTORY 5.1b.
+    if (shift) {
+        auto kern = interp_planned_shift_kernel<T>;
+        S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        kern<<<grid, 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,
+                                     static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles, tiles_per_xcd,
+                                     chunks_per_block, n_chunks, tail, tail_split);
         S3_LAUNCH_CHECK();
         return S3_OK;
     }
@@ -1551,13 +1398,13 @@ static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows
         S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         kern<<<grid, 512, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,
                                      static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles, tiles_per_xcd,
-                                     chunks_per_block, n_chunks, brick, gy, tail, tail_split);
+                                     chunks_per_block, n_chunks, tail, tail_split);
     } else {
         auto kern = interp_planned_kernel<T, 64>;
         S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         kern<<<grid, 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,
                                      static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles, tiles_per_xcd,
-                                     chunks_per_block, n_chunks, brick, gy, tail, tail_split);
+                                     chunks_per_block, n_chunks, tail, tail_split);
     }
     S3_LAUNCH_CHECK();
     return S3_OK;
@@ -1578,7 +1425,7 @@ __global__ void __launch_bounds__(256, 2)
 plan_loads_kernel(const int32_t *__restrict__ tile_row_begin, const int32_t *__restrict__ rows, const char *__restrict__ data,
                   uint64_t stride_bytes, uint64_t row_bytes, int n_lines, int64_t n_tiles, int64_t tiles_per_xcd, float *__restrict__ sink) {
     extern __shared__ float4 lds_raw[];
-    const int64_t tile = (int64_t)(blockIdx.x & 7) * tiles_per_xcd + (blockIdx.x >> 3);      // XCD-aware, tile order (brick_map, n_split = 1)
+    const int64_t tile = (int64_t)(blockIdx.x & 7) * tiles_per_xcd + (blockIdx.x >> 3);      // XCD-aware, tile order (run_map, one run per tile)
     if (tile >= n_tiles) return;
     const int r_begin = tile_row_begin[tile], n_r = tile_row_begin[tile + 1] - r_begin;
     const int srow = threadIdx.x >> 3, svec = threadIdx.x & 7;
@@ -1638,10 +1485,6 @@ plan_loads_kernel(const int32_t *__restrict__ tile_row_begin, const int32_t *__r
 }
 
 extern "C" {
-
-#ifdef S3_PROBE_STAMPS
-int s3_probe_read(long long *h, int n) { return (int)hipMemcpyFromSymbol(h, HIP_SYMBOL(s3_probe_stamps), sizeof(long long) * n); }
-#endif
 
 void s3_interp_plan_destroy(s3_interp_plan *p) {
     if (!p) return;
@@ -1886,11 +1729,6 @@ int s3_interp_planned_src(s3_interp_plan *p, const void *d_table, int dtype, int
     return planned_dispatch(p, p->rows_src, p->n_table, "s3_interp_planned_src", d_table, dtype, row_len, in_stride, d_out, stream);
 }
 
-
-int s3_debug_reload_env(void) {
-    s3::switches() = s3::parse_switches();
-    return S3_OK;
-}
 
 // yardstick: see plan_loads_kernel.  The table is the one s3_interp_planned_src reads (after s3_interp_plan_set_source_ids) or, with
 // n_table_rows == 0, the compacted table of s3_interp_planned.  *h_staged_bytes = rows staged over all tiles x lines x 128.

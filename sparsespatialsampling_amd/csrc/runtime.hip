@@ -73,11 +73,8 @@ int upload_threads() {
 // ... for LARGE uploads only: a small batch's staging lines are still in the last-level cache when the DMA engine comes for them
 // (16 buffers of 8 MB), and streaming them to DRAM first makes it slower.  MI355X host, batches back to back, download of the
 // previous batch running (tools/e2e_probe.py; streamed / cached): 243 MB (25 snapshots) 9.7 / 6.5-7.2 ms, 1.94 GB (200) 44.2 /
-// 45.7-53.0 ms, 9.7 GB (1000) 225 / 263-266 ms.  S3_UPLOAD_NT=0 / 1 forces one form.
-bool upload_streaming_stores(int64_t total_bytes) {
-    static const int v = [] { const char *e = getenv("S3_UPLOAD_NT"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-    return v < 0 ? total_bytes >= ((int64_t)1 << 30) : v == 1;
-}
+// 45.7-53.0 ms, 9.7 GB (1000) 225 / 263-266 ms.
+bool upload_streaming_stores(int64_t total_bytes) { return total_bytes >= ((int64_t)1 << 30); }
 
 // The host cores next to the GPU.  On a two-socket host a transfer thread on the far socket packs into pinned memory the DMA engine
 // reads across the socket link, and the Linux scheduler puts a process's threads on either socket as it likes: 25-snapshot batches
@@ -298,18 +295,7 @@ static int upload_rows_impl(const void *h_src, const int32_t *h_rows, int64_t n_
         }
         l.next = b;
     };
-    const bool trace = getenv("S3_UPLOAD_TRACE") != nullptr;
-    const auto t_begin = std::chrono::steady_clock::now();
-    const auto t_spawned = std::chrono::steady_clock::now();
     g_pool.run(n_thr, work);
-    if (trace) {
-        const auto t_end = std::chrono::steady_clock::now();
-        (void)hipStreamSynchronize(st);
-        const auto t_sync = std::chrono::steady_clock::now();
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "[s3_upload] %lld rows x %lld B, %lld chunks, %d threads: spawn %.2f ms, packed+queued %.2f ms, transfers done %.2f ms\n",
-                (long long)n_rows, (long long)row_bytes, (long long)n_chunks, n_thr, ms(t_begin, t_spawned), ms(t_begin, t_end), ms(t_begin, t_sync));
-    }
     S3_HIP_CHECK((hipError_t)first_error.load());
     return S3_OK;
 } catch (const std::exception &e) {          // thread creation
@@ -373,16 +359,12 @@ int s3_download(void *h_dst, const void *d_src, size_t bytes, s3_stream stream) 
         OnGpuNode near(dev, false);
         if (hipSetDevice(dev) != hipSuccess) { first_error = (int)hipErrorInvalidDevice; return; }
         UploadLane &l = g_lanes[t];
-        static const bool keep = [] { const char *e = getenv("S3_DOWNLOAD_KEEP_STREAMS"); return !(e && e[0] == '0'); }();
-        hipStream_t fresh = nullptr;
-        if (!keep) {
-            if (hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking) != hipSuccess) { first_error = (int)hipErrorUnknown; return; }
-        } else if (!l.down && hipStreamCreateWithFlags(&l.down, hipStreamNonBlocking) != hipSuccess) {
+        if (!l.down && hipStreamCreateWithFlags(&l.down, hipStreamNonBlocking) != hipSuccess) {
             l.down = nullptr;
             first_error = (int)hipErrorUnknown;
             return;
         }
-        const hipStream_t own = keep ? l.down : fresh;
+        const hipStream_t own = l.down;
         int64_t pending[UP_BUFS] = {-1, -1};                              // chunk sitting in each pinned buffer
         auto drain = [&](int b) {
             if (pending[b] < 0) return hipSuccess;
@@ -409,7 +391,6 @@ int s3_download(void *h_dst, const void *d_src, size_t bytes, s3_stream stream) 
         }
         for (int k = 0; k < UP_BUFS && e == hipSuccess; ++k) e = drain((b + k) % UP_BUFS);
         (void)hipStreamSynchronize(own);
-        if (fresh) (void)hipStreamDestroy(fresh);
         if (e != hipSuccess) first_error = (int)e;
     };
     g_pool.run(n_thr, work);

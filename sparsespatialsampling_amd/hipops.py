@@ -6,7 +6,6 @@ current HIP stream.  Every function below ends in exactly one hand-written HIP k
 operator runs on the hot path.  All tensors passed in must live on the current CUDA(HIP) device and be contiguous.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch as pt
@@ -212,26 +211,6 @@ def snapshot_major_rows(values, n_comp, n_snapshots, rows, n_out, out_ptr):
                                                 int(n_out), C.c_void_p(int(out_ptr)), _stream()), "s3_snapshot_major_rows")
 
 
-_LAUNCH_SWITCHES = ("S3_PLAN_MIN_BLOCKS", "S3_STREAM_MIN_TILES", "S3_STREAM_MAX_CHUNKS", "S3_INPLACE_SHIFT", "S3_SHIFT_MIN_CHUNKS",
-                    "S3_SHORT_STREAM", "S3_SHORT_NO_QUAD", "S3_SHORT_LDS_WEIGHTS", "S3_PLAN_SPLIT", "S3_PLAN_BRICK", "S3_PLAN_TAIL",
-                    "S3_OUT_HOLD")
-_switch_state = [None]
-
-
-def reload_env():
-    """the library parses its S3_* launch switches once; tell it to read them again (A/B tools, tests)"""
-    check(_lib.hip_lib().s3_debug_reload_env(), "s3_debug_reload_env")
-    _switch_state[0] = tuple(os.environ.get(k) for k in _LAUNCH_SWITCHES)
-
-
-def _sync_switches():
-    """a switch flipped through ``os.environ`` since the last planned launch reaches the library before the next one
-    (``os.environ`` is the interpreter's own dict: reading it races with nothing)"""
-    now = tuple(os.environ.get(k) for k in _LAUNCH_SWITCHES)
-    if now != _switch_state[0]:
-        reload_env()
-
-
 class InterpPlan:
     """De-duplicated, LDS-tiled form of a static neighbour table (s3_interp_plan_*): build once per KNN cache, reuse for
     every snapshot batch.  ``centers`` (cell centres, [nc, dim]) gives the Hilbert-curve processing order."""
@@ -340,7 +319,6 @@ class InterpPlan:
         row_len, in_stride, out = self._check_batch(data, out, "interp")
         if w is not self._w_ref or w._version != self._w_version:    # another tensor, or modified through torch: re-attach
             self.set_weights(w)
-        _sync_switches()
         check(_lib.hip_lib().s3_interp_planned(self._handle, C.c_void_p(0), C.c_void_p(data.data_ptr()),
                                                DTYPE_CODE[data.dtype], row_len, in_stride, _ptr(out), _stream()),
               "s3_interp_planned")
@@ -376,7 +354,6 @@ class InterpPlan:
         if int(table.shape[0]) != self.n_table or table.dtype not in DTYPE_CODE:
             raise TypeError("InterpPlan.interp_src: the table does not match the ids given to set_source_ids")
         row_len, in_stride, out = self._check_batch(table, out, "interp_src")
-        _sync_switches()
         check(_lib.hip_lib().s3_interp_planned_src(self._handle, C.c_void_p(table.data_ptr()), DTYPE_CODE[table.dtype],
                                                    self.n_table, row_len, in_stride, _ptr(out), _stream()),
               "s3_interp_planned_src")

@@ -189,20 +189,25 @@ def test_interp_planned_short_and_ragged_rows(ops, orc, row_len, dtype):
                                                  # two to four vectors per row: the narrow layout (four lanes per row, eight passes)
                                                  (16, pt.float32, False), (16, pt.float32, True), (12, pt.float32, True), (13, pt.float32, False),
                                                  (8, pt.float64, False), (6, pt.float64, True), (7, pt.float32, True)])
-def test_stream_kernel_equals_direct(ops, orc, monkeypatch, k, d, row_len, dtype, dense):
+def test_stream_kernel_equals_direct(ops, orc, k, d, row_len, dtype, dense):
     """the persistent kernel (interp_planned_stream_kernel: the reference's neighbour counts, rows of more than four 16-byte
     vectors -- the 25-snapshot batches of examples/s3_for_cylinder3D_Re3900.py:28-69 as scalar (100 B) and 3-component
     (300 B) rows) on pitched batches and on DENSE batches read where they lie (element-aligned rows, ragged tails loaded as
     the last vector of the row): bit-equal to the direct gather kernel, 1e-13 against the oracle; also with fewer tiles
-    than persistent workgroups and with partial tiles"""
-    monkeypatch.setenv("S3_STREAM_MIN_TILES", "1")
+    than persistent workgroups (2 per CU: 512 on MI355X) and with partial tiles.  Element-aligned rows take the persistent
+    kernel at any plan size: the 65- and 1-cell plans leave most XCDs' tile lists empty.  On those two plans 16-byte aligned
+    rows take the chunk and short-row kernels (fewer than 64 tiles)."""
     rng = np.random.default_rng(row_len * 7 + k)
-    for n, nc in ((30_000, 7_777), (400, 65), (3000, 1)):
+    for n, nc in ((30_000, 7_777), (12_000, 4_201), (400, 65), (3000, 1)):
         x, c = rng.random((n, d)), rng.random((nc, d)) * 1.2 - 0.1
         knn = ops.KnnIndex(x)
         idx, dist = knn.query(c, k)
         w = ops.idw_weights(dist)
         plan = ops.InterpPlan(idx, n, c)
+        if nc >= 4_096:                                 # plans meant for the persistent kernel on 16-byte aligned rows too
+            assert plan.n_tiles >= 64                   # the smallest plan it takes them on
+        if nc == 4_201:                                 # (not a multiple of 64 cells: partial tiles)
+            assert plan.n_tiles < 512                   # fewer tiles than persistent workgroups
         if dense:
             data = pt.empty((n, row_len), dtype=dtype, device="cuda")
         else:
@@ -260,7 +265,7 @@ def test_interp_src_reads_the_full_table_in_place(ops, orc, row_len, dtype):
     (1000, pt.float32, "dense"),        # 4000-byte rows: starts 0 / 32 / 64 / 96 bytes into a line (the bench's batch)
     (1004, pt.float32, "dense"),        # 4016-byte rows: every phase 0 .. 7
     (300, pt.float32, "dense"),         # ten chunks, the last one a 48-byte tail
-    (200, pt.float32, "dense"),         # seven chunks: the shortest rows that take the shift kernel (S3_SHIFT_MIN_CHUNKS = 6) ...
+    (200, pt.float32, "dense"),         # seven chunks: the shortest rows that take the shift kernel (six chunks and more) ...
     (152, pt.float32, "dense"),         # ... and five: the persistent kernel with straddling segments
     (1001, pt.float32, "pitch+3"),      # ragged rows in a 16-byte pitch
     (514, pt.float64, "dense"),         # f64: 4112-byte rows
@@ -270,8 +275,9 @@ def test_interp_src_reads_the_full_table_in_place(ops, orc, row_len, dtype):
 def test_shift_kernel_reads_rows_off_the_line_grid(ops, orc, row_len, dtype, layout):
     """long rows that start on 16-byte but not on 128-byte boundaries (a dense [N, n_comp * T] batch read where it lies,
     reference export.py:446-468) take interp_planned_shift_kernel: whole aligned lines per load, the per-row phase undone
-    on the way into LDS.  Same bits as the direct kernel and as the straddling form (S3_INPLACE_SHIFT=0); the oracle on top."""
-    import os
+    on the way into LDS.  Same bits as the direct kernel and as the straddling form (a plan of 128-cell tiles, which takes
+    interp_planned_kernel<T,128>); the oracle on top.  The 5 000-cell plan fills less than the chip: the chunks of a tile are
+    split over several workgroups."""
     rng = np.random.default_rng(row_len)
     n, nc, k = 50_000, 5_000, 26
     x, c = rng.random((n, 3)), rng.random((nc, 3)) * 0.5 + 0.25
@@ -303,21 +309,11 @@ def test_shift_kernel_reads_rows_off_the_line_grid(ops, orc, row_len, dtype, lay
     plan.set_source_ids(used.contiguous(), n)
     got = plan.interp_src(table)
     assert pt.equal(got, direct)
-    os.environ["S3_INPLACE_SHIFT"] = "0"
-    try:
-        assert pt.equal(plan.interp_src(table), direct)
-    finally:
-        del os.environ["S3_INPLACE_SHIFT"]
-    # the optional forms of the same launch: whole-line output stores (cells whose output row starts mid-line hold their last 64
-    # bytes back one step), no finer grain at the end of the launch, the tail cut differently -- the same bits every time
-    for env in ({"S3_OUT_HOLD": "1"}, {"S3_PLAN_MIN_BLOCKS": "1", "S3_PLAN_TAIL": "0"}, {"S3_PLAN_MIN_BLOCKS": "1", "S3_PLAN_TAIL": "7x3", "S3_OUT_HOLD": "1"},
-                {"S3_PLAN_MIN_BLOCKS": "1", "S3_PLAN_TAIL": "100x5"}, {"S3_PLAN_SPLIT": "3", "S3_PLAN_BRICK": "5"}):
-        os.environ.update(env)
-        try:
-            assert pt.equal(plan.interp_src(table), direct), env
-        finally:
-            for kk in env:
-                del os.environ[kk]
+    plan128 = ops.InterpPlan(idx_c, int(used.numel()), c, tile_cells=128)     # straddling 128-byte segments
+    plan128.set_weights(w)
+    plan128.set_source_ids(used.contiguous(), n)
+    assert pt.equal(plan128.interp_src(table), direct)
+    plan128.close()
     ref = orc.interp(w.cpu().numpy(), idx.cpu().numpy(), table.contiguous().cpu().numpy().reshape(n, 1, row_len)).reshape(nc, row_len)
     assert np.abs(got.cpu().numpy() - ref).max() <= 1e-13 * np.abs(ref).max()
     # the plan over ALL rows (no source ids): s3_interp_planned on the same table
@@ -331,7 +327,7 @@ def test_default_tail_map_with_ragged_chunk_counts(ops, row_len):
     """the DEFAULT launch form of the chunk kernels on a large plan (only the A/B switches covered it): with >= 256 tiles
     per XCD and >= 8 chunks the last 32 tiles of every XCD's share are cut into 4 runs of chunks (tail_map) -- here with chunk
     counts that the 4 runs do not divide (8, 9 and 13 chunks: runs of 2 / 3 / 4 with a short or empty last one) on dense rows off
-    the line grid (the shift kernel).  Same bits as the direct gather kernel; switching the tail off changes nothing."""
+    the line grid (the shift kernel).  Same bits as the direct gather kernel."""
     rng = np.random.default_rng(row_len)
     n, nc, k = 300_000, 160_000, 26
     x, c = rng.random((n, 3)), rng.random((nc, 3))
@@ -350,12 +346,6 @@ def test_default_tail_map_with_ragged_chunk_counts(ops, row_len):
     plan.set_weights(w)
     plan.set_source_ids(used.contiguous(), n)
     assert pt.equal(plan.interp_src(table), direct)
-    os.environ["S3_PLAN_TAIL"] = "0"
-    try:
-        assert pt.equal(plan.interp_src(table), direct)
-    finally:
-        del os.environ["S3_PLAN_TAIL"]
-    assert pt.equal(plan.interp_src(table), direct)      # (and the switch went back with the environment)
     plan.close()
 
 

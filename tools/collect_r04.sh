@@ -18,7 +18,6 @@ if [ "$lease" = "1" ]; then
     cd $root
     S3_BENCH_SHARE_GPU=1 S3_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
         --master-port 29655 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_2ranks_one_gpu.json 2> $out/bench_2ranks_one_gpu.err
-    python tools/ab_inplace.py 1000 200 > $out/ab_inplace.txt 2>&1
     python tools/e2e_probe.py 200 > $out/e2e_probe_T200.txt 2>&1
     python tools/e2e_probe.py 25 12 > $out/e2e_probe_T25.txt 2>&1
     python tools/transport_probe.py 1.0 > $out/transport_probe.txt 2>&1

@@ -1,7 +1,7 @@
-"""dev helper: steady-state time per batch of ExportData._fit_data on the bench grid (host batches back to back), with the
-download of a batch completing behind the next batch's upload (default) or waited for in the call (S3_EXPORT_DEFER=0)
+"""dev helper: steady-state time per batch of ExportData._fit_data on the bench grid (host batches back to back; the download
+of a batch completes behind the next batch's upload)
     python tools/e2e_probe.py T [reps]"""
-import os, sys, time, types, logging
+import sys, time, types, logging
 import numpy as np, torch as pt
 sys.path.insert(0, ".")
 import bench
@@ -26,8 +26,7 @@ data = pt.empty((n, 1, t), dtype=pt.float32).normal_()
 for _ in range(2):
     ex._fit_data(coords, data, "f", 10 ** 9)
 pt.cuda.synchronize()
-for mode in ("1", "0", "1", "0"):
-    os.environ["S3_EXPORT_DEFER"] = mode
+for rnd in range(2):
     pt.cuda.synchronize()
     t0 = time.perf_counter()
     calls = []
@@ -37,5 +36,5 @@ for mode in ("1", "0", "1", "0"):
         calls.append((time.perf_counter() - c0) * 1e3)
     pt.cuda.synchronize()
     dt = (time.perf_counter() - t0) / reps * 1e3
-    print(f"T={t} defer={mode}: {dt:.1f} ms per batch ({nc * t / dt / 1e6:.2f} G cell*snapshots/s); host time per call " +
+    print(f"T={t} round {rnd}: {dt:.1f} ms per batch ({nc * t / dt / 1e6:.2f} G cell*snapshots/s); host time per call " +
           " ".join(f"{c:.1f}" for c in calls), flush=True)
