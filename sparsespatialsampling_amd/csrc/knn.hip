@@ -18,6 +18,7 @@
 // -ffp-contract=off): rdist = sum_j (q_j-p_j)^2 in dimension order, dist = sqrt(rdist), w = 1/dist, numpy pairwise
 // summation of y*w and w.  Ties in rdist are ordered by the original point id.
 #include "common.h"
+#include "scan_sort.h"
 
 #include <cfloat>
 #include <cstdlib>
@@ -80,6 +81,17 @@ __device__ __forceinline__ int cell_coord(const Grid<DIM> &g, double x, int j) {
     return (int)t;
 }
 
+// inclusive scan of v over a group of W lanes (gl = lane within the group)
+template <int W, typename T>
+__device__ __forceinline__ T group_scan(T v, int gl) {
+#pragma unroll
+    for (int d = 1; d < W; d <<= 1) {
+        const T u = __shfl_up(v, d, W);
+        if (gl >= d) v += u;
+    }
+    return v;
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // build kernels
 // ------------------------------------------------------------------------------------------------------------------
@@ -121,62 +133,6 @@ __global__ void cell_count_kernel(Grid<DIM> g, const double *__restrict__ pts, i
     for (int j = DIM - 1; j >= 0; --j) c = c * g.res[j] + cell_coord<DIM>(g, pts[i * DIM + j], j);
     cid[i] = (int32_t)c;
     atomicAdd(&count[c], 1);
-}
-
-// exclusive scan, 1024 items per block (4 per thread), three passes
-__global__ void scan_block_kernel(int32_t *__restrict__ data, int64_t n, int32_t *__restrict__ block_sums) {
-    __shared__ int32_t s[256];
-    int64_t base = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    int32_t v[4], t = 0;
-    for (int j = 0; j < 4; ++j) {
-        v[j] = (base + j < n) ? data[base + j] : 0;
-        t += v[j];
-    }
-    s[threadIdx.x] = t;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        int32_t add = ((int)threadIdx.x >= off) ? s[threadIdx.x - off] : 0;
-        __syncthreads();
-        s[threadIdx.x] += add;
-        __syncthreads();
-    }
-    int32_t excl = s[threadIdx.x] - t;
-    for (int j = 0; j < 4; ++j) {
-        if (base + j < n) data[base + j] = excl;
-        excl += v[j];
-    }
-    if (threadIdx.x == 255) block_sums[blockIdx.x] = s[255];
-}
-
-__global__ void scan_sums_kernel(int32_t *__restrict__ block_sums, int64_t nb) {
-    // single block, serial over chunks of 256
-    __shared__ int32_t s[256];
-    __shared__ int32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nb; base += 256) {
-        int64_t i = base + threadIdx.x;
-        int32_t t = i < nb ? block_sums[i] : 0;
-        s[threadIdx.x] = t;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            int32_t add = ((int)threadIdx.x >= off) ? s[threadIdx.x - off] : 0;
-            __syncthreads();
-            s[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < nb) block_sums[i] = carry + s[threadIdx.x] - t;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += s[255];
-        __syncthreads();
-    }
-}
-
-__global__ void scan_add_kernel(int32_t *__restrict__ data, int64_t n, const int32_t *__restrict__ block_sums) {
-    int64_t base = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    int32_t add = block_sums[blockIdx.x];
-    for (int j = 0; j < 4; ++j)
-        if (base + j < n) data[base + j] += add;
 }
 
 template <int DIM>
@@ -262,12 +218,7 @@ sub_scan_kernel(const int32_t *__restrict__ cell_start, const uint8_t *__restric
     for (int base = 0; base < n; base += 64) {
         const int i = base + threadIdx.x;
         const int32_t v = i < n ? t[i] : 0;
-        int32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int32_t u = __shfl_up(incl, off, 64);
-            if ((int)threadIdx.x >= off) incl += u;
-        }
+        const int32_t incl = group_scan<64>(v, (int)threadIdx.x);
         if (i < n) t[i] = carry + incl - v;
         carry += __shfl(incl, 63, 64);
     }
@@ -591,25 +542,21 @@ idw_predict_kernel(Grid<DIM> g, const double *__restrict__ pts, const int32_t *_
     yhat[i] = idw_from_list(b, y);
 }
 
-// a3+a4 first half: query t = (cell i, point j) with j = 0 the cell centre and j = 1..2^DIM its candidate children.
-// REUSE: the centre of new cell first + i IS candidate child (i mod 2^DIM) of its parent, a point whose metric was
-// predicted (by this kernel, from the same coordinates: make_children_kernel and the expression below are the same) when
-// the parent was created -- the reference predicts it again (s_cube.py:221-233) and gets the same number, so only the
-// 2^DIM child points are searched here and the centre's value is taken from child_metric[parent].  Either way the child
-// values of every new cell are kept in child_metric[cell] for the day the cell is refined.
-template <int DIM, bool REUSE>
+// a3+a4 first half: query t = (cell i, point j) with j = 0 the cell centre and j = 1..2^DIM its candidate children, one lane
+// each (s3_child_gain, and s3_child_gain_reuse without parents).  With child_metric, the child values of every new cell are kept
+// in child_metric[cell] for the day the cell is refined.
+template <int DIM>
 __global__ void __launch_bounds__(KNN_BLOCK)
 child_metric_kernel(Grid<DIM> g, const double *__restrict__ pts, const int32_t *__restrict__ orig,
                     const int32_t *__restrict__ cs, const double *__restrict__ y, const double *__restrict__ center,
                     const int32_t *__restrict__ level, int64_t first, int64_t n, double quarter_width, int k,
-                    double *__restrict__ metric_all, const int32_t *__restrict__ parents, int64_t parents_offset,
-                    double *__restrict__ child_metric) {
-    constexpr int NCH = 1 << DIM, NQ = NCH + 1, PER = REUSE ? NCH : NQ;
+                    double *__restrict__ metric_all, double *__restrict__ child_metric) {
+    constexpr int NCH = 1 << DIM, NQ = NCH + 1;
     extern __shared__ double lds[];
     int64_t t = blockIdx.x * (int64_t)KNN_BLOCK + threadIdx.x;
-    if (t >= n * PER) return;
-    int64_t i = t / PER;
-    int jq = (int)(t - i * PER) + (REUSE ? 1 : 0);
+    if (t >= n * NQ) return;
+    int64_t i = t / NQ;
+    int jq = (int)(t - i * NQ);
     int64_t cell = first + i;
     double q[DIM];
     double off = cell_offset(quarter_width, level[cell]);
@@ -623,10 +570,6 @@ child_metric_kernel(Grid<DIM> g, const double *__restrict__ pts, const int32_t *
     const double m = idw_from_list(b, y);
     metric_all[i * NQ + jq] = m;
     if (child_metric != nullptr && jq > 0) child_metric[cell * NCH + jq - 1] = m;
-    if (REUSE && jq == 1) {
-        const int64_t ii = parents_offset + i;               // position of the cell among the batch's children
-        metric_all[i * NQ] = child_metric[(int64_t)parents[ii / NCH] * NCH + (ii % NCH)];
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -647,8 +590,8 @@ child_metric_kernel(Grid<DIM> g, const double *__restrict__ pts, const int32_t *
 //      original point id) against the others, the k best land in order -- the k nearest neighbours exactly as the per-lane
 //      search returns them, since every point nearer than the safe radius is in the box;
 //   5. inverse-distance prediction with numpy's pairwise order (eight partial sums on eight lanes).
-// Cells the wavefront cannot take are searched the per-lane way by 2^DIM of its lanes on the spot: the results are the same
-// bits either way (tools/knn_coop_probe.py, every refine golden).
+// The child points of cells the wavefront cannot take go on to the streaming stages below and then to the per-lane search: the
+// results are the same bits either way (tests/test_gpu_knn_coop.py, every refine golden).
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int COOP_M = 384;        // candidates per cell held in LDS
 constexpr int COOP_SLOTS = COOP_M / 64;
@@ -685,6 +628,235 @@ __device__ __forceinline__ void wave_sync_lds() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// ---- stages shared by the three wavefront solvers (coop_solve, near_solve, far_solve) -------------------------------------------
+// A group of W lanes answers one query point (gl = the lane within the group): W = 64 / 2^DIM in coop_solve and near_solve, 64 in
+// far_solve.  The stages hand back values; what to do when one cannot answer (give up for the whole wavefront, or carry a group's
+// failure on) stays with the solver.  LDS arrays are passed as references to their __shared__ rows, never as pointers.
+
+// any lane of the group
+template <int W>
+__device__ __forceinline__ bool group_any(bool v) {
+    if constexpr (W == 64) return __ballot(v) != 0ull;
+#pragma unroll
+    for (int d = 1; d < W; d <<= 1) v |= __shfl_xor((int)v, d, W) != 0;
+    return v;
+}
+
+// Limits of the box of buckets [lo_i, hi_i] for query q.  A point nearer than the safe radius lies in the box: the squared
+// distance to the nearest face with buckets behind it, less 1e-9 hmin (0 when q is at or beyond such a face; out: how far q lies
+// outside the grid along each axis -- the points beyond face j are at least that far along the other axes too).  lim2 = the
+// safe radius, or just beyond the box's farthest corner when no face limits it (whole_grid).  inside: q lies strictly inside
+// every limiting face (coop_solve gives up on a point that is not, so the 0 never reaches it).
+struct BoxLimits {
+    double lim2;
+    bool inside, whole_grid;
+};
+
+template <int DIM>
+__device__ __forceinline__ BoxLimits box_limits(const Grid<DIM> &g, const double (&q)[DIM], const int (&lo_i)[3], const int (&hi_i)[3],
+                                                double hmin, const double *out = nullptr, double out2 = 0.0) {
+    BoxLimits r{0.0, true, true};
+    double safe2 = DBL_MAX, far2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) {
+        const double face_lo = g.lo[j] + (double)lo_i[j] * g.h[j], face_hi = g.lo[j] + (double)(hi_i[j] + 1) * g.h[j];
+        const double others2 = out != nullptr ? fmax(out2 - out[j] * out[j], 0.0) : 0.0;
+        auto limit = [&](double f) {
+            r.inside = r.inside && f > 0.0;
+            r.whole_grid = false;
+            safe2 = fmin(safe2, f > 0.0 ? (out != nullptr ? f * f + others2 : f * f) : 0.0);
+        };
+        if (lo_i[j] > 0) limit(q[j] - face_lo - 1e-9 * hmin);                 // buckets behind this face were not visited
+        if (hi_i[j] < g.res[j] - 1) limit(face_hi - q[j] - 1e-9 * hmin);
+        const double span = fmax(fabs(q[j] - face_lo), fabs(face_hi - q[j]));
+        far2 += span * span;
+    }
+    r.lim2 = fmin(safe2, far2 * 1.0000001 + 1e-300);
+    return r;
+}
+
+// The bin of the group's histogram (NB bins; lane gl owns bins gl * BPL ..) in which the running count reaches k, broadcast to
+// the group with the count up to and including it (below); total = the whole count (b_star = -1 when it is below k).
+struct KthBin {
+    int b_star;
+    uint32_t below, total;
+};
+
+template <int W, int NB, int N>
+__device__ __forceinline__ KthBin kth_bin(const uint32_t (&hist)[N], int gl, int k) {
+    constexpr int BPL = NB / W;
+    static_assert(NB % W == 0 && NB <= N, "the group's lanes own exactly the NB bins");
+    uint32_t bins[BPL], mine = 0;
+#pragma unroll
+    for (int b = 0; b < BPL; ++b) {
+        bins[b] = hist[gl * BPL + b];
+        mine += bins[b];
+    }
+    const uint32_t upto = group_scan<W>(mine, gl);
+    KthBin r{-1, 0u, __shfl(upto, W - 1, W)};
+    uint32_t run = upto - mine;
+    const bool owner = run < (uint32_t)k && upto >= (uint32_t)k;       // exactly one lane of the group
+#pragma unroll
+    for (int b = 0; b < BPL; ++b) {
+        run += bins[b];
+        if (owner && r.b_star < 0 && run >= (uint32_t)k) { r.b_star = gl * BPL + b; r.below = run; }
+    }
+#pragma unroll
+    for (int d = 1; d < W; d <<= 1) {                         // the owner's values to the whole group
+        r.b_star = max(r.b_star, __shfl_xor(r.b_star, d, W));
+        r.below = max(r.below, __shfl_xor(r.below, d, W));
+    }
+    return r;
+}
+
+// near_solve and far_solve: one pass over the M slots of the group's box, the points read from the index, UNROLL slots of a lane
+// in flight (their positions, then their coordinates, then the use): use(p, d) for every point p whose squared distance d is
+// below lim2.  (coop_solve's passes read the coordinates it cached in LDS, slot by slot: they stay its own.)
+template <int DIM, int W, int UNROLL, typename PointOf, typename Use>
+__device__ __forceinline__ void stream_box(const double *__restrict__ pts, const double (&q)[DIM], int M, int gl, double lim2,
+                                           PointOf &&point_of, Use &&use) {
+    auto dist2 = [&](int p) {
+        double d = 0.0;
+#pragma unroll
+        for (int j = 0; j < DIM; ++j) {
+            const double u = q[j] - pts[(int64_t)p * DIM + j];
+            d += u * u;
+        }
+        return d;
+    };
+    for (int t0 = gl; t0 < M; t0 += UNROLL * W) {
+        int p[UNROLL];
+        double d[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) p[u] = point_of(min(t0 + W * u, M - 1));
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) d[u] = dist2(p[u]);
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u)
+            if (t0 + W * u < M && d[u] < lim2) use(p[u], d[u]);
+    }
+}
+
+// Every entry of the group's short list (n_list of them; lane gl holds entries gl + r W) ranked by counting: less = how many
+// entries are nearer.  tie: two entries at exactly the same distance among the k that matter (lattices of points) -- the order
+// among them is the original point id, left to the per-lane search, which breaks the tie that way.
+template <int W>
+struct Ranked {
+    static constexpr int ROUNDS = COOP_CAP / W < 1 ? 1 : COOP_CAP / W;
+    static_assert(ROUNDS * W >= COOP_CAP, "every entry of the list has a lane");
+    double d[ROUNDS];
+    int32_t p[ROUNDS], less[ROUNDS];
+    bool tie;
+};
+
+template <int W, bool SAME_LENGTHS = false>
+__device__ __forceinline__ Ranked<W> rank_list(const double (&list_d)[COOP_CAP], const int32_t (&list_p)[COOP_CAP], int n_list,
+                                               int k, int gl) {
+    constexpr int ROUNDS = Ranked<W>::ROUNDS;
+    Ranked<W> e;
+    int32_t same[ROUNDS];
+    const int last = max(n_list - 1, 0);                      // (n_list = 0: a group of near_solve that failed)
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+        const int at = min(gl + r * W, last);
+        e.d[r] = list_d[at];
+        e.p[r] = list_p[at];
+        e.less[r] = same[r] = 0;
+    }
+    if constexpr (SAME_LENGTHS) {
+        // coop_solve: the groups' lists are of nearly the same length across the wavefront (one cell's child points), the rounds
+        // beyond them are skipped; near_solve's groups answer unrelated queries, for which that test diverges
+        const int n_rounds = (n_list + W - 1) / W;
+#pragma unroll 4
+        for (int m = 0; m < n_list; ++m) {                    // every entry of the list against this lane's entries
+            const double dm = list_d[m];
+#pragma unroll
+            for (int r = 0; r < ROUNDS; ++r)
+                if (r < n_rounds) {
+                    e.less[r] += dm < e.d[r] ? 1 : 0;
+                    same[r] += dm == e.d[r] ? 1 : 0;
+                }
+        }
+    } else {
+        for (int m = 0; m < n_list; ++m) {
+            const double dm = list_d[m];
+#pragma unroll
+            for (int r = 0; r < ROUNDS; ++r) {
+                e.less[r] += dm < e.d[r] ? 1 : 0;
+                same[r] += dm == e.d[r] ? 1 : 0;
+            }
+        }
+    }
+    e.tie = false;
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) e.tie |= gl + r * W < n_list && same[r] > 1 && e.less[r] < k;
+    return e;
+}
+
+// the kk best (kk = 0: a failed group, which loads nothing) to their places in the lists: distance, value and inverse-distance
+// weight, by the lanes that hold them -- one round trip for all values
+template <int W>
+__device__ __forceinline__ void place_best(const Ranked<W> &e, int n_list, int kk, int gl, const double *__restrict__ y,
+                                           double (&list_d)[COOP_CAP], double (&list_y)[COOP_CAP], double (&list_w)[COOP_CAP]) {
+    constexpr int ROUNDS = Ranked<W>::ROUNDS;
+    double e_y[ROUNDS];
+    bool best[ROUNDS];
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+        best[r] = gl + r * W < n_list && e.less[r] < kk;
+        e_y[r] = best[r] ? y[e.p[r]] : 0.0;
+    }
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r)
+        if (best[r]) {
+            list_d[e.less[r]] = e.d[r];
+            list_y[e.less[r]] = e_y[r];
+            list_w[e.less[r]] = 1.0 / sqrt(e.d[r]);
+        }
+}
+
+// inverse-distance prediction from the kk best in order, as idw_from_list / numpy_pairwise above: a zero distance weighs 1 and the
+// others 0; eight partial sums on lanes 0 .. 7 of the group.  The value is lane 0's.
+template <int W>
+__device__ __forceinline__ double idw_best(const double (&list_d)[COOP_CAP], const double (&list_y)[COOP_CAP],
+                                           const double (&list_w)[COOP_CAP], int kk, int gl) {
+    bool zero = false;
+    for (int m = gl; m < kk; m += W) zero |= list_d[m] == 0.0;
+    zero = group_any<W>(zero);
+    auto wgt = [&](int m) { return zero ? (list_d[m] == 0.0 ? 1.0 : 0.0) : list_w[m]; };
+    auto term = [&](int m) { return list_y[m] * wgt(m); };
+    double num = 0.0, den = 0.0;
+    if (kk < 8) {
+        if (gl == 0)
+            for (int m = 0; m < kk; ++m) {
+                num += term(m);
+                den += wgt(m);
+            }
+    } else {
+        double rn = 0.0, rw = 0.0;
+        if (gl < 8) {
+            rn = term(gl);
+            rw = wgt(gl);
+            for (int m = 8; m < kk - (kk % 8); m += 8) {
+                rn += term(m + gl);
+                rw += wgt(m + gl);
+            }
+        }
+        // ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) on lane 0 of the group
+        rn += __shfl_xor(rn, 1, W); rw += __shfl_xor(rw, 1, W);        // lanes 0,2,4,6: r0+r1, r2+r3, ...
+        rn += __shfl_xor(rn, 2, W); rw += __shfl_xor(rw, 2, W);        // lanes 0,4: (r0+r1)+(r2+r3), (r4+r5)+(r6+r7)
+        rn += __shfl_xor(rn, 4, W); rw += __shfl_xor(rw, 4, W);
+        num = rn;
+        den = rw;
+        if (gl == 0)
+            for (int m = kk - (kk % 8); m < kk; ++m) {
+                num += term(m);
+                den += wgt(m);
+            }
+    }
+    return num / den;
+}
+
 // One cooperative search: the 64 / LPQ query points c + dir(jq) * off (LPQ lanes each; LPQ = 64: the single point c) share
 // the box around the bucket of c.  reach = radius (in bucket sides, per axis) the box must cover around the query points:
 // the expected distance of the k-th neighbour at the index's average occupancy times a margin.  Returns false (for the
@@ -696,11 +868,9 @@ template <int DIM, int LPQ>
 __device__ __forceinline__ int coop_solve(const Grid<DIM> &g, const double *__restrict__ pts, const int32_t *__restrict__ orig,
                                            const int32_t *__restrict__ cs, const double *__restrict__ y, CoopLds<DIM> &L,
                                            const double (&c)[DIM], double off, int k, double reach, int lane, double &result) {
-    constexpr int BPL = COOP_NB / LPQ < 1 ? 1 : COOP_NB / LPQ;
     constexpr int CHUNK = LPQ >= 64 ? 2 : 4;                  // candidates whose coordinates a lane reads together
-    constexpr int ROUNDS = COOP_CAP / LPQ < 1 ? 1 : COOP_CAP / LPQ;
     constexpr int NQB = 64 / LPQ;
-    static_assert(LPQ >= 8 && (COOP_NB % LPQ == 0 || LPQ > COOP_NB) && COOP_CAP <= 64, "lane layout");
+    static_assert(LPQ >= 8 && COOP_CAP <= 64, "lane layout");
 
     // ---- 1. the box: as many buckets on either side of the centre's bucket as the query points' reach needs ---------------
     int lo_i[3] = {0, 0, 0}, hi_i[3] = {0, 0, 0};
@@ -729,12 +899,7 @@ __device__ __forceinline__ int coop_solve(const Grid<DIM> &g, const double *__re
         if (g.sub_res != nullptr)
             for (int x = lo_i[0]; x <= hi_i[0]; ++x) refined |= g.sub_res[row + x] != 0;
     }
-    int incl = my_cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int u = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += u;
-    }
+    const int incl = group_scan<64>(my_cnt, lane);
     const int M = __shfl(incl, 63, 64);
     if (__ballot(refined) != 0ull || M > COOP_M || M < k) return 2;
     wave_sync_lds();                                          // (an earlier attempt's reads of these arrays are done)
@@ -779,27 +944,12 @@ __device__ __forceinline__ int coop_solve(const Grid<DIM> &g, const double *__re
 
     // ---- 3. this lane's query point, its safe radius, ONE pass over the distances (kept in registers) ----------------------
     const int jq = lane / LPQ, gl = lane - jq * LPQ;
-    double q[DIM], safe2 = DBL_MAX, far2 = 0.0;
-    bool inside = true;
+    double q[DIM];
 #pragma unroll
-    for (int j = 0; j < DIM; ++j) {
-        q[j] = NQB == 1 ? c[j] : c[j] + dir_comp(DIM, jq, j) * off;
-        const double face_lo = g.lo[j] + (double)lo_i[j] * g.h[j], face_hi = g.lo[j] + (double)(hi_i[j] + 1) * g.h[j];
-        if (lo_i[j] > 0) {                                    // buckets behind this face exist and were not visited
-            const double f = q[j] - face_lo - 1e-9 * hmin;
-            inside = inside && f > 0.0;
-            safe2 = fmin(safe2, f * f);
-        }
-        if (hi_i[j] < g.res[j] - 1) {
-            const double f = face_hi - q[j] - 1e-9 * hmin;
-            inside = inside && f > 0.0;
-            safe2 = fmin(safe2, f * f);
-        }
-        const double span = fmax(fabs(q[j] - face_lo), fabs(face_hi - q[j]));
-        far2 += span * span;
-    }
-    if (__ballot(!inside) != 0ull) return 1;                  // a query point at or beyond a face of the box
-    const double lim2 = fmin(safe2, far2 * 1.0000001 + 1e-300);   // no limiting face: every point of the grid is in the box
+    for (int j = 0; j < DIM; ++j) q[j] = NQB == 1 ? c[j] : c[j] + dir_comp(DIM, jq, j) * off;
+    const BoxLimits box = box_limits<DIM>(g, q, lo_i, hi_i, hmin);
+    if (__ballot(!box.inside) != 0ull) return 1;              // a query point at or beyond a face of the box
+    const double lim2 = box.lim2;
     const double to_bin = (double)COOP_NB / lim2;
     auto dist2 = [&](int t) {
         double d = 0.0;
@@ -820,37 +970,8 @@ __device__ __forceinline__ int coop_solve(const Grid<DIM> &g, const double *__re
             if (t0 + u * LPQ < M && d[u] < lim2) atomicAdd(&L.hist[jq][min(COOP_NB - 1, (int)(d[u] * to_bin))], 1u);
     }
     wave_sync_lds();
-    // the bin in which the count reaches k: lane gl of the group owns bins gl * BPL .. (lanes beyond the bins: none)
-    uint32_t bins[BPL], mine = 0;
-#pragma unroll
-    for (int b = 0; b < BPL; ++b) {
-        bins[b] = gl * BPL + b < COOP_NB ? L.hist[jq][gl * BPL + b] : 0u;
-        mine += bins[b];
-    }
-    uint32_t upto = mine;
-#pragma unroll
-    for (int d = 1; d < LPQ; d <<= 1) {
-        const uint32_t u = __shfl_up(upto, d, LPQ);
-        if (gl >= d) upto += u;
-    }
-    const uint32_t total = __shfl(upto, LPQ - 1, LPQ);
-    int b_star = -1;
-    uint32_t below = 0;
-    {
-        uint32_t run = upto - mine;
-        const bool owner = run < (uint32_t)k && upto >= (uint32_t)k;       // exactly one lane of the group
-#pragma unroll
-        for (int b = 0; b < BPL; ++b) {
-            run += bins[b];
-            if (owner && b_star < 0 && run >= (uint32_t)k) { b_star = gl * BPL + b; below = run; }
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < LPQ; d <<= 1) {                       // the owner's values to the whole group
-        b_star = max(b_star, __shfl_xor(b_star, d, LPQ));
-        below = max(below, __shfl_xor(below, d, LPQ));
-    }
-    if (__ballot(total < (uint32_t)k || below > (uint32_t)COOP_CAP) != 0ull) return 2;
+    const KthBin kb = kth_bin<LPQ, COOP_NB>(L.hist[jq], gl, k);
+    if (__ballot(kb.total < (uint32_t)k || kb.below > (uint32_t)COOP_CAP) != 0ull) return 2;
 
     // ---- 4. short list, ranks, the k best in order -----------------------------------------------------------------------
     for (int t0 = gl; t0 < M; t0 += CHUNK * LPQ) {           // (the distances again: cheaper than 2 x 48 registers per lane)
@@ -859,94 +980,22 @@ __device__ __forceinline__ int coop_solve(const Grid<DIM> &g, const double *__re
         for (int u = 0; u < CHUNK; ++u) d[u] = dist2(min(t0 + u * LPQ, M - 1));
 #pragma unroll
         for (int u = 0; u < CHUNK; ++u)
-            if (t0 + u * LPQ < M && d[u] < lim2 && min(COOP_NB - 1, (int)(d[u] * to_bin)) <= b_star) {
+            if (t0 + u * LPQ < M && d[u] < lim2 && min(COOP_NB - 1, (int)(d[u] * to_bin)) <= kb.b_star) {
                 const uint32_t at = atomicAdd(&L.count[jq], 1u);
                 L.list_d[jq][at] = d[u];
                 L.list_p[jq][at] = L.pos[t0 + u * LPQ];
             }
     }
     wave_sync_lds();
-    const int n_list = (int)below;
-    double e_d[ROUNDS];
-    int32_t e_p[ROUNDS], e_less[ROUNDS], e_same[ROUNDS];
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        const int e = min(gl + r * LPQ, n_list - 1);
-        e_d[r] = L.list_d[jq][e];
-        e_p[r] = L.list_p[jq][e];
-        e_less[r] = e_same[r] = 0;
-    }
-    const int n_rounds = (n_list + LPQ - 1) / LPQ;            // (uniform within the group, nearly always within the wavefront)
-#pragma unroll 4
-    for (int m = 0; m < n_list; ++m) {                        // every entry of the list against this lane's entries
-        const double dm = L.list_d[jq][m];
-#pragma unroll
-        for (int r = 0; r < ROUNDS; ++r)
-            if (r < n_rounds) {
-                e_less[r] += dm < e_d[r] ? 1 : 0;
-                e_same[r] += dm == e_d[r] ? 1 : 0;
-            }
-    }
-    // two entries at exactly the same distance among the ones that matter (lattices of points): the order among them is
-    // the original point id -- left to the per-lane search, which breaks the tie that way
-    bool tie = false;
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) tie |= gl + r * LPQ < n_list && e_same[r] > 1 && e_less[r] < k;
-    if (__ballot(tie) != 0ull) return 2;
+    const int n_list = (int)kb.below;
+    const Ranked<LPQ> e = rank_list<LPQ, true>(L.list_d[jq], L.list_p[jq], n_list, k, gl);
+    if (__ballot(e.tie) != 0ull) return 2;
     wave_sync_lds();
-    // value and inverse-distance weight of the k best, by the lanes that hold them: one round trip for all values
-    double e_y[ROUNDS];
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        if (!(gl + r * LPQ < n_list)) e_less[r] = COOP_CAP;
-        e_y[r] = e_less[r] < k ? y[e_p[r]] : 0.0;
-    }
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r)
-        if (e_less[r] < k) {
-            L.list_d[jq][e_less[r]] = e_d[r];
-            L.best.list_y[jq][e_less[r]] = e_y[r];
-            L.best.list_w[jq][e_less[r]] = 1.0 / sqrt(e_d[r]);
-        }
+    place_best<LPQ>(e, n_list, k, gl, y, L.list_d[jq], L.best.list_y[jq], L.best.list_w[jq]);
     wave_sync_lds();
 
-    // ---- 5. inverse-distance prediction, numpy's pairwise order (idw_from_list / numpy_pairwise above) --------------------
-    bool zero = false;
-    for (int m = gl; m < k; m += LPQ) zero |= L.list_d[jq][m] == 0.0;
-#pragma unroll
-    for (int d = 1; d < LPQ; d <<= 1) zero |= __shfl_xor((int)zero, d, LPQ) != 0;
-    auto wgt = [&](int m) { return zero ? (L.list_d[jq][m] == 0.0 ? 1.0 : 0.0) : L.best.list_w[jq][m]; };
-    auto term = [&](int m) { return L.best.list_y[jq][m] * wgt(m); };
-    double num = 0.0, den = 0.0;
-    if (k < 8) {
-        if (gl == 0)
-            for (int m = 0; m < k; ++m) {
-                num += term(m);
-                den += wgt(m);
-            }
-    } else {
-        double rn = 0.0, rw = 0.0;
-        if (gl < 8) {
-            rn = term(gl);
-            rw = wgt(gl);
-            for (int m = 8; m < k - (k % 8); m += 8) {
-                rn += term(m + gl);
-                rw += wgt(m + gl);
-            }
-        }
-        // ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) on lane 0 of the group
-        rn += __shfl_xor(rn, 1, LPQ); rw += __shfl_xor(rw, 1, LPQ);        // lanes 0,2,4,6: r0+r1, r2+r3, ...
-        rn += __shfl_xor(rn, 2, LPQ); rw += __shfl_xor(rw, 2, LPQ);        // lanes 0,4: (r0+r1)+(r2+r3), (r4+r5)+(r6+r7)
-        rn += __shfl_xor(rn, 4, LPQ); rw += __shfl_xor(rw, 4, LPQ);
-        num = rn;
-        den = rw;
-        if (gl == 0)
-            for (int m = k - (k % 8); m < k; ++m) {
-                num += term(m);
-                den += wgt(m);
-            }
-    }
-    result = num / den;
+    // ---- 5. inverse-distance prediction, numpy's pairwise order ----------------------------------------------------------
+    result = idw_best<LPQ>(L.list_d[jq], L.best.list_y[jq], L.best.list_w[jq], k, gl);
     wave_sync_lds();
     return 0;
 }
@@ -965,7 +1014,9 @@ child_metric_coop_kernel(Grid<DIM> g, const double *__restrict__ pts, const int3
     if (i >= n) return;                                       // (uniform per wavefront)
     CoopLds<DIM> &L = lds_all[threadIdx.x >> 6];
     const int64_t cell = first + i;
-    // the centre's value from the parent's entry
+    // the centre's value from the parent's entry: the centre of new cell first + i IS candidate child (i mod 2^DIM) of its
+    // parent, a point whose metric was predicted from the same coordinates (make_children_kernel and the child points here are the
+    // same expression) when the parent was created -- the reference predicts it again (s_cube.py:221-233) and gets the same number
     if (lane == 0) {
         const int64_t ii = parents_offset + i;
         metric_all[i * NQ] = child_metric[(int64_t)parents[ii / NCH] * NCH + (ii % NCH)];
@@ -1030,8 +1081,7 @@ __device__ __forceinline__ bool far_solve(const Grid<DIM> &g, const double *__re
     //  point is at least D_i away along that axis, so the box need not be a cube around the query and the points beyond a face
     //  of axis j are at least sqrt(f_j^2 + sum_{i != j} D_i^2) away)
     int lo_i[3] = {0, 0, 0}, hi_i[3] = {0, 0, 0};
-    double hmin = DBL_MAX, hmax = 0.0, safe2 = DBL_MAX, far2 = 0.0, out[3] = {0.0, 0.0, 0.0}, out2 = 0.0;
-    bool whole_grid = true;
+    double hmin = DBL_MAX, hmax = 0.0, out[3] = {0.0, 0.0, 0.0}, out2 = 0.0;
 #pragma unroll
     for (int j = 0; j < DIM; ++j) {
         hmin = fmin(hmin, g.h[j]);
@@ -1058,23 +1108,7 @@ __device__ __forceinline__ bool far_solve(const Grid<DIM> &g, const double *__re
         lo_i[j] = max(b - r_lo, 0);
         hi_i[j] = min(b + r_hi, g.res[j] - 1);
     }
-#pragma unroll
-    for (int j = 0; j < DIM; ++j) {
-        const double face_lo = g.lo[j] + (double)lo_i[j] * g.h[j], face_hi = g.lo[j] + (double)(hi_i[j] + 1) * g.h[j];
-        const double others2 = fmax(out2 - out[j] * out[j], 0.0);
-        if (lo_i[j] > 0) {
-            const double f = q[j] - face_lo - 1e-9 * hmin;
-            safe2 = fmin(safe2, f > 0.0 ? f * f + others2 : 0.0);
-            whole_grid = false;
-        }
-        if (hi_i[j] < g.res[j] - 1) {
-            const double f = face_hi - q[j] - 1e-9 * hmin;
-            safe2 = fmin(safe2, f > 0.0 ? f * f + others2 : 0.0);
-            whole_grid = false;
-        }
-        const double span = fmax(fabs(q[j] - face_lo), fabs(face_hi - q[j]));
-        far2 += span * span;
-    }
+    const BoxLimits box = box_limits<DIM>(g, q, lo_i, hi_i, hmin, out, out2);
     const int ny = hi_i[1] - lo_i[1] + 1, nz = DIM == 3 ? hi_i[2] - lo_i[2] + 1 : 1, n_rows = ny * nz;
     if (n_rows > FAR_ROWS) { hopeless = true; return false; }
     wave_sync_lds();
@@ -1092,20 +1126,15 @@ __device__ __forceinline__ bool far_solve(const Grid<DIM> &g, const double *__re
         if (g.sub_res != nullptr)
             for (int x = lo_i[0]; x <= hi_i[0]; ++x) refined |= g.sub_res[row + x] != 0;
     }
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int u = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += u;
-    }
+    const int incl = group_scan<64>(mine, lane);
     const int M = __shfl(incl, 63, 64);
     for (int r = r0; r < r1; ++r) L.row_prefix[r] += incl - mine;
     if (lane == 0) L.count = 0;
     for (int t = lane; t < FAR_NB; t += 64) L.hist[t] = 0;
     if (__ballot(refined) != 0ull || M > FAR_MAX_POINTS) { hopeless = true; return false; }
-    if (M < k) { hopeless = whole_grid; return false; }      // a wider box will do (unless this one is the whole grid)
+    if (M < k) { hopeless = box.whole_grid; return false; }  // a wider box will do (unless this one is the whole grid)
     wave_sync_lds();
-    const double lim2 = fmin(safe2, far2 * 1.0000001 + 1e-300);
+    const double lim2 = box.lim2;
     if (!(lim2 > out2)) return false;
     // (no point is nearer than the grid: the bins span out2 .. lim2, or the candidates of a query far outside would share a few)
     const double to_bin = (double)FAR_NB / (lim2 - out2);
@@ -1117,131 +1146,28 @@ __device__ __forceinline__ bool far_solve(const Grid<DIM> &g, const double *__re
             if (r + step < n_rows && L.row_prefix[r + step] <= t) r += step;
         return L.row_start[r] + (t - L.row_prefix[r]);
     };
-    auto dist2 = [&](int p) {
-        double d = 0.0;
-#pragma unroll
-        for (int j = 0; j < DIM; ++j) {
-            const double u = q[j] - pts[(int64_t)p * DIM + j];
-            d += u * u;
-        }
-        return d;
-    };
     // ---- pass A: histogram ---------------------------------------------------------------------------------------------------
-    for (int t0 = lane; t0 < M; t0 += FAR_UNROLL * 64) {
-        int p[FAR_UNROLL];
-        double d[FAR_UNROLL];
-#pragma unroll
-        for (int u = 0; u < FAR_UNROLL; ++u) p[u] = point_of(min(t0 + 64 * u, M - 1));
-#pragma unroll
-        for (int u = 0; u < FAR_UNROLL; ++u) d[u] = dist2(p[u]);
-#pragma unroll
-        for (int u = 0; u < FAR_UNROLL; ++u)
-            if (t0 + 64 * u < M && d[u] < lim2) atomicAdd(&L.hist[bin_of(d[u])], 1u);
-    }
+    stream_box<DIM, 64, FAR_UNROLL>(pts, q, M, lane, lim2, point_of, [&](int, double d) { atomicAdd(&L.hist[bin_of(d)], 1u); });
     wave_sync_lds();
-    constexpr int BPL = FAR_NB / 64;
-    uint32_t bins[BPL], own = 0;
-#pragma unroll
-    for (int b = 0; b < BPL; ++b) {
-        bins[b] = L.hist[lane * BPL + b];
-        own += bins[b];
-    }
-    uint32_t upto = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(upto, d, 64);
-        if (lane >= d) upto += u;
-    }
-    const uint32_t total = __shfl(upto, 63, 64);
-    int b_star = -1;
-    uint32_t below = 0;
-    {
-        uint32_t run = upto - own;
-        const bool owner = run < (uint32_t)k && upto >= (uint32_t)k;
-#pragma unroll
-        for (int b = 0; b < BPL; ++b) {
-            run += bins[b];
-            if (owner && b_star < 0 && run >= (uint32_t)k) { b_star = lane * BPL + b; below = run; }
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        b_star = max(b_star, __shfl_xor(b_star, d, 64));
-        below = max(below, __shfl_xor(below, d, 64));
-    }
-    if (total < (uint32_t)k) { hopeless = whole_grid; return false; }
-    if (below > (uint32_t)COOP_CAP) { hopeless = true; return false; }     // ties in bulk
+    const KthBin kb = kth_bin<64, FAR_NB>(L.hist, lane, k);
+    if (kb.total < (uint32_t)k) { hopeless = box.whole_grid; return false; }
+    if (kb.below > (uint32_t)COOP_CAP) { hopeless = true; return false; }  // ties in bulk
     // ---- pass B: the candidates below the threshold ---------------------------------------------------------------------------
-    for (int t0 = lane; t0 < M; t0 += FAR_UNROLL * 64) {
-        int p[FAR_UNROLL];
-        double d[FAR_UNROLL];
-#pragma unroll
-        for (int u = 0; u < FAR_UNROLL; ++u) p[u] = point_of(min(t0 + 64 * u, M - 1));
-#pragma unroll
-        for (int u = 0; u < FAR_UNROLL; ++u) d[u] = dist2(p[u]);
-#pragma unroll
-        for (int u = 0; u < FAR_UNROLL; ++u)
-            if (t0 + 64 * u < M && d[u] < lim2 && bin_of(d[u]) <= b_star) {
-                const uint32_t at = min(atomicAdd(&L.count, 1u), (uint32_t)(COOP_CAP - 1));
-                L.list_d[at] = d[u];
-                L.list_p[at] = p[u];
-            }
-    }
-    wave_sync_lds();
-    const int n_list = (int)below;
-    const int e = min(lane, n_list - 1);
-    const double e_d = L.list_d[e];
-    const int e_p = L.list_p[e];
-    int less = 0, same = 0;
-    for (int m = 0; m < n_list; ++m) {
-        const double dm = L.list_d[m];
-        less += dm < e_d ? 1 : 0;
-        same += dm == e_d ? 1 : 0;
-    }
-    if (__ballot(lane < n_list && same > 1 && less < k) != 0ull) { hopeless = true; return false; }   // a tie that matters
-    wave_sync_lds();
-    const bool best = lane < n_list && less < k;
-    const double e_y = best ? y[e_p] : 0.0;
-    if (best) {
-        L.list_d[less] = e_d;
-        L.list_y[less] = e_y;
-        L.list_w[less] = 1.0 / sqrt(e_d);
-    }
-    wave_sync_lds();
-    bool zero = false;
-    for (int m = lane; m < k; m += 64) zero |= L.list_d[m] == 0.0;
-    zero = __ballot(zero) != 0ull;
-    auto wgt = [&](int m) { return zero ? (L.list_d[m] == 0.0 ? 1.0 : 0.0) : L.list_w[m]; };
-    auto term = [&](int m) { return L.list_y[m] * wgt(m); };
-    double num = 0.0, den = 0.0;
-    if (k < 8) {
-        if (lane == 0)
-            for (int m = 0; m < k; ++m) {
-                num += term(m);
-                den += wgt(m);
-            }
-    } else {
-        double rn = 0.0, rw = 0.0;
-        if (lane < 8) {
-            rn = term(lane);
-            rw = wgt(lane);
-            for (int m = 8; m < k - (k % 8); m += 8) {
-                rn += term(m + lane);
-                rw += wgt(m + lane);
-            }
+    stream_box<DIM, 64, FAR_UNROLL>(pts, q, M, lane, lim2, point_of, [&](int p, double d) {
+        if (bin_of(d) <= kb.b_star) {
+            const uint32_t at = min(atomicAdd(&L.count, 1u), (uint32_t)(COOP_CAP - 1));
+            L.list_d[at] = d;
+            L.list_p[at] = p;
         }
-        rn += __shfl_xor(rn, 1, 64); rw += __shfl_xor(rw, 1, 64);
-        rn += __shfl_xor(rn, 2, 64); rw += __shfl_xor(rw, 2, 64);
-        rn += __shfl_xor(rn, 4, 64); rw += __shfl_xor(rw, 4, 64);
-        num = rn;
-        den = rw;
-        if (lane == 0)
-            for (int m = k - (k % 8); m < k; ++m) {
-                num += term(m);
-                den += wgt(m);
-            }
-    }
-    result = num / den;
+    });
+    wave_sync_lds();
+    const int n_list = (int)kb.below;
+    const Ranked<64> e = rank_list<64>(L.list_d, L.list_p, n_list, k, lane);
+    if (__ballot(e.tie) != 0ull) { hopeless = true; return false; }   // a tie that matters
+    wave_sync_lds();
+    place_best<64>(e, n_list, k, lane, y, L.list_d, L.list_y, L.list_w);
+    wave_sync_lds();
+    result = idw_best<64>(L.list_d, L.list_y, L.list_w, k, lane);
     return true;
 }
 
@@ -1274,14 +1200,12 @@ __device__ __forceinline__ bool near_solve(const Grid<DIM> &g, const double *__r
                                            int k, double reach, int lane, double &result) {
     constexpr int NQB = 1 << DIM, LPQ = 64 / NQB, ROWS = NearLds<DIM>::ROWS;
     constexpr int MAXC = (ROWS + LPQ - 1) / LPQ;              // rows per lane
-    constexpr int BPL = COOP_NB / LPQ, ROUNDS = COOP_CAP / LPQ;
-    static_assert(COOP_NB % LPQ == 0 && COOP_CAP % LPQ == 0, "lane layout");
     const int jq = lane / LPQ, gl = lane - jq * LPQ;
     bool fail = !active || k > COOP_CAP;
 
     // ---- the box and its rows ----------------------------------------------------------------------------------------------
     int lo_i[3] = {0, 0, 0}, hi_i[3] = {0, 0, 0};
-    double hmin = DBL_MAX, safe2 = DBL_MAX, far2 = 0.0;
+    double hmin = DBL_MAX;
 #pragma unroll
     for (int j = 0; j < DIM; ++j) {
         const int b = cell_coord<DIM>(g, q[j], j);
@@ -1292,20 +1216,7 @@ __device__ __forceinline__ bool near_solve(const Grid<DIM> &g, const double *__r
         hi_i[j] = min(b + r_hi, g.res[j] - 1);
         hmin = fmin(hmin, g.h[j]);
     }
-#pragma unroll
-    for (int j = 0; j < DIM; ++j) {
-        const double face_lo = g.lo[j] + (double)lo_i[j] * g.h[j], face_hi = g.lo[j] + (double)(hi_i[j] + 1) * g.h[j];
-        if (lo_i[j] > 0) {
-            const double f = q[j] - face_lo - 1e-9 * hmin;
-            safe2 = fmin(safe2, f > 0.0 ? f * f : 0.0);
-        }
-        if (hi_i[j] < g.res[j] - 1) {
-            const double f = face_hi - q[j] - 1e-9 * hmin;
-            safe2 = fmin(safe2, f > 0.0 ? f * f : 0.0);
-        }
-        const double span = fmax(fabs(q[j] - face_lo), fabs(face_hi - q[j]));
-        far2 += span * span;
-    }
+    const BoxLimits box = box_limits<DIM>(g, q, lo_i, hi_i, hmin);
     const int ny = hi_i[1] - lo_i[1] + 1, nz = DIM == 3 ? hi_i[2] - lo_i[2] + 1 : 1, n_rows = fail ? 0 : ny * nz;
     int r_start[MAXC], r_cnt[MAXC];
     bool refined = false;
@@ -1326,12 +1237,7 @@ __device__ __forceinline__ bool near_solve(const Grid<DIM> &g, const double *__r
     int M = 0;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
-        int incl = r_cnt[c];
-#pragma unroll
-        for (int d = 1; d < LPQ; d <<= 1) {
-            const int u = __shfl_up(incl, d, LPQ);
-            if (gl >= d) incl += u;
-        }
+        const int incl = group_scan<LPQ>(r_cnt[c], gl);
         const int r = c * LPQ + gl;
         if (r < n_rows) {
             L.row_start[jq][r] = r_start[c];
@@ -1339,15 +1245,15 @@ __device__ __forceinline__ bool near_solve(const Grid<DIM> &g, const double *__r
         }
         M += __shfl(incl, LPQ - 1, LPQ);
     }
-#pragma unroll
-    for (int d = 1; d < LPQ; d <<= 1) refined |= __shfl_xor((int)refined, d, LPQ) != 0;
-    const double lim2 = fmin(safe2, far2 * 1.0000001 + 1e-300);
+    refined = group_any<LPQ>(refined);
+    const double lim2 = box.lim2;
     fail = fail || refined || M < k || M > NEAR_MAX_POINTS || !(lim2 > 0.0);
     if (fail) M = 0;
     if (lane < NQB) L.count[lane] = 0;
     for (int t = lane; t < NQB * (COOP_NB + 1); t += 64) (&L.hist[0][0])[t] = 0;
     wave_sync_lds();
     const double to_bin = (double)COOP_NB / (lim2 > 0.0 ? lim2 : 1.0);
+    auto bin_of = [&](double d) { return min(COOP_NB - 1, (int)(d * to_bin)); };
     auto point_of = [&](int t) {                             // slot t of the group's box -> position in the index
         int r = 0;
 #pragma unroll
@@ -1355,152 +1261,29 @@ __device__ __forceinline__ bool near_solve(const Grid<DIM> &g, const double *__r
             if (step < ROWS && r + step < n_rows && L.row_prefix[jq][r + step] <= t) r += step;
         return L.row_start[jq][r] + (t - L.row_prefix[jq][r]);
     };
-    auto dist2 = [&](int p) {
-        double d = 0.0;
-#pragma unroll
-        for (int j = 0; j < DIM; ++j) {
-            const double u = q[j] - pts[(int64_t)p * DIM + j];
-            d += u * u;
-        }
-        return d;
-    };
     // ---- pass A: histogram of the squared distances inside the safe radius ------------------------------------------------------
-    for (int t0 = gl; t0 < M; t0 += 4 * LPQ) {
-        int p[4];
-        double d[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] = point_of(min(t0 + LPQ * u, M - 1));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) d[u] = dist2(p[u]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (t0 + LPQ * u < M && d[u] < lim2) atomicAdd(&L.hist[jq][min(COOP_NB - 1, (int)(d[u] * to_bin))], 1u);
-    }
+    stream_box<DIM, LPQ, 4>(pts, q, M, gl, lim2, point_of, [&](int, double d) { atomicAdd(&L.hist[jq][bin_of(d)], 1u); });
     wave_sync_lds();
-    uint32_t bins[BPL], mine = 0;
-#pragma unroll
-    for (int b = 0; b < BPL; ++b) {
-        bins[b] = L.hist[jq][gl * BPL + b];
-        mine += bins[b];
-    }
-    uint32_t upto = mine;
-#pragma unroll
-    for (int d = 1; d < LPQ; d <<= 1) {
-        const uint32_t u = __shfl_up(upto, d, LPQ);
-        if (gl >= d) upto += u;
-    }
-    const uint32_t total = __shfl(upto, LPQ - 1, LPQ);
-    int b_star = -1;
-    uint32_t below = 0;
-    {
-        uint32_t run = upto - mine;
-        const bool owner = run < (uint32_t)k && upto >= (uint32_t)k;
-#pragma unroll
-        for (int b = 0; b < BPL; ++b) {
-            run += bins[b];
-            if (owner && b_star < 0 && run >= (uint32_t)k) { b_star = gl * BPL + b; below = run; }
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < LPQ; d <<= 1) {
-        b_star = max(b_star, __shfl_xor(b_star, d, LPQ));
-        below = max(below, __shfl_xor(below, d, LPQ));
-    }
-    fail = fail || total < (uint32_t)k || below > (uint32_t)COOP_CAP;
-    if (fail) { M = 0; below = 0; }
+    KthBin kb = kth_bin<LPQ, COOP_NB>(L.hist[jq], gl, k);
+    fail = fail || kb.total < (uint32_t)k || kb.below > (uint32_t)COOP_CAP;
+    if (fail) { M = 0; kb.below = 0; }
     // ---- pass B: the candidates below the threshold -> the group's short list ---------------------------------------------------
-    for (int t0 = gl; t0 < M; t0 += 4 * LPQ) {
-        int p[4];
-        double d[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] = point_of(min(t0 + LPQ * u, M - 1));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) d[u] = dist2(p[u]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (t0 + LPQ * u < M && d[u] < lim2 && min(COOP_NB - 1, (int)(d[u] * to_bin)) <= b_star) {
-                const uint32_t at = min(atomicAdd(&L.count[jq], 1u), (uint32_t)(COOP_CAP - 1));
-                L.list_d[jq][at] = d[u];
-                L.list_p[jq][at] = p[u];
-            }
-    }
-    wave_sync_lds();
-    const int n_list = (int)below;
-    double e_d[ROUNDS];
-    int32_t e_p[ROUNDS], e_less[ROUNDS], e_same[ROUNDS];
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        const int e = max(min(gl + r * LPQ, n_list - 1), 0);
-        e_d[r] = L.list_d[jq][e];
-        e_p[r] = L.list_p[jq][e];
-        e_less[r] = e_same[r] = 0;
-    }
-    for (int m = 0; m < n_list; ++m) {
-        const double dm = L.list_d[jq][m];
-#pragma unroll
-        for (int r = 0; r < ROUNDS; ++r) {
-            e_less[r] += dm < e_d[r] ? 1 : 0;
-            e_same[r] += dm == e_d[r] ? 1 : 0;
+    stream_box<DIM, LPQ, 4>(pts, q, M, gl, lim2, point_of, [&](int p, double d) {
+        if (bin_of(d) <= kb.b_star) {
+            const uint32_t at = min(atomicAdd(&L.count[jq], 1u), (uint32_t)(COOP_CAP - 1));
+            L.list_d[jq][at] = d;
+            L.list_p[jq][at] = p;
         }
-    }
-    bool tie = false;
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) tie |= gl + r * LPQ < n_list && e_same[r] > 1 && e_less[r] < k;
-#pragma unroll
-    for (int d = 1; d < LPQ; d <<= 1) tie |= __shfl_xor((int)tie, d, LPQ) != 0;
-    fail = fail || tie;
+    });
+    wave_sync_lds();
+    const int n_list = (int)kb.below;
+    const Ranked<LPQ> e = rank_list<LPQ>(L.list_d[jq], L.list_p[jq], n_list, k, gl);
+    fail = fail || group_any<LPQ>(e.tie);
     wave_sync_lds();
     const int kk = fail ? 0 : k;                              // (a failed group loads and sums nothing: its lists hold no data)
-    double e_y[ROUNDS];
-    bool e_best[ROUNDS];
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        e_best[r] = gl + r * LPQ < n_list && e_less[r] < kk;
-        e_y[r] = e_best[r] ? y[e_p[r]] : 0.0;
-    }
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r)
-        if (e_best[r]) {
-            L.list_d[jq][e_less[r]] = e_d[r];
-            L.list_y[jq][e_less[r]] = e_y[r];
-            L.list_w[jq][e_less[r]] = 1.0 / sqrt(e_d[r]);
-        }
+    place_best<LPQ>(e, n_list, kk, gl, y, L.list_d[jq], L.list_y[jq], L.list_w[jq]);
     wave_sync_lds();
-    bool zero = false;
-    for (int m = gl; m < kk; m += LPQ) zero |= L.list_d[jq][m] == 0.0;
-#pragma unroll
-    for (int d = 1; d < LPQ; d <<= 1) zero |= __shfl_xor((int)zero, d, LPQ) != 0;
-    auto wgt = [&](int m) { return zero ? (L.list_d[jq][m] == 0.0 ? 1.0 : 0.0) : L.list_w[jq][m]; };
-    auto term = [&](int m) { return L.list_y[jq][m] * wgt(m); };
-    double num = 0.0, den = 0.0;
-    if (kk < 8) {
-        if (gl == 0)
-            for (int m = 0; m < kk; ++m) {
-                num += term(m);
-                den += wgt(m);
-            }
-    } else {
-        double rn = 0.0, rw = 0.0;
-        if (gl < 8) {
-            rn = term(gl);
-            rw = wgt(gl);
-            for (int m = 8; m < kk - (kk % 8); m += 8) {
-                rn += term(m + gl);
-                rw += wgt(m + gl);
-            }
-        }
-        rn += __shfl_xor(rn, 1, LPQ); rw += __shfl_xor(rw, 1, LPQ);
-        rn += __shfl_xor(rn, 2, LPQ); rw += __shfl_xor(rw, 2, LPQ);
-        rn += __shfl_xor(rn, 4, LPQ); rw += __shfl_xor(rw, 4, LPQ);
-        num = rn;
-        den = rw;
-        if (gl == 0)
-            for (int m = kk - (kk % 8); m < kk; ++m) {
-                num += term(m);
-                den += wgt(m);
-            }
-    }
-    result = num / den;
+    result = idw_best<LPQ>(L.list_d[jq], L.list_y[jq], L.list_w[jq], kk, gl);
     return !fail;
 }
 
@@ -1668,6 +1451,56 @@ static int check_query_args(const s3_knn *knn, const void *q, int64_t nq, int k,
     return S3_OK;
 }
 
+// how far (in bucket sides) the wavefront kernels' boxes reach beyond the child points: the radius of the ball that holds k points
+// at the index's average occupancy times this margin; where the cloud is thinner than that the wavefront notices (fewer than k
+// candidates inside its safe radius) and leaves the query to the next stage
+constexpr double COOP_MARGIN = 1.15;
+
+template <int DIM>
+static int child_metric_launch(const s3_knn *knn, int k, const double *d_center, const int32_t *d_level, int64_t first, int64_t n,
+                                double qw, double *d_scratch, const int32_t *d_parents, int64_t parents_offset,
+                                double *d_child_metric, hipStream_t st) {
+    constexpr int NCH = 1 << DIM;
+    const Grid<DIM> g = make_grid<DIM>(knn);
+    const size_t lds = knn_lds_bytes(k);
+    if (d_parents == nullptr) {                               // every point of every cell, one lane each
+        child_metric_kernel<DIM><<<grid_for(n * (NCH + 1), KNN_BLOCK), KNN_BLOCK, lds, st>>>(
+            g, knn->pts, knn->orig, knn->cell_start, knn->y, d_center, d_level, first, n, qw, k, d_scratch, d_child_metric);
+        return S3_OK;
+    }
+    // The wavefront kernels, for cells whose centre value is their parent's child value:
+    //   coop -- one wavefront per cell, one shared box;  near -- what that leaves (cells too large for one box: the uniform
+    //   levels, the first adaptive batches), 2^dim queries per wavefront, each its own small box;  far -- what that leaves (next
+    //   to a body, at the edge of the cloud, outside it), one wavefront per query, boxes of growing size;  rest -- per lane.
+    // Measured on MI355X (rocprofv3 per launch): cylinder3D, adaptive batches of ~40 000 new cells: 0.37 + 0.08 + 0.21 ms against
+    // 1.16 ms for the per-lane kernel alone, the first adaptive batch 0.47 + 0.53 + 1.1 ms, the batches of the uniform levels
+    // 0.1 - 0.3 ms instead of 0.4 - 1.4 ms (a per-lane wavefront lives that long however few queries it has); refine
+    // 0.058 -> 0.050 s on one box.  box5e7, batches of ~230 000 fine cells: 3.8 - 4.2 + 0.5 - 1.1 + 0.05 ms against 7.0 ms,
+    // refine 0.70 -> 0.57 s.
+    const double occupancy = (double)knn->n / (double)knn->ncell;
+    const double ball = DIM == 3 ? std::cbrt(3.0 * k / (4.0 * 3.14159265358979323846 * occupancy))
+                                 : std::sqrt(k / (3.14159265358979323846 * occupancy));
+    const double reach = ball * COOP_MARGIN;
+    // behind the n * (2^dim + 1) doubles of d_scratch: two lists (counter, pad, entries) that the kernels hand on in turns:
+    // coop -> rest -> near -> rest2 -> far -> rest (emptied in between) -> per-lane kernel
+    int32_t *d_rest = reinterpret_cast<int32_t *>(d_scratch + n * (NCH + 1));
+    int32_t *d_rest2 = d_rest + 2 + n * NCH;
+    S3_HIP_CHECK(hipMemsetAsync(d_rest, 0, 2 * sizeof(int32_t), st));
+    S3_HIP_CHECK(hipMemsetAsync(d_rest2, 0, 2 * sizeof(int32_t), st));
+    child_metric_coop_kernel<DIM><<<grid_for(n, COOP_WAVES), 64 * COOP_WAVES, 0, st>>>(
+        g, knn->pts, knn->orig, knn->cell_start, knn->y, d_center, d_level, first, n, qw, k, reach, d_scratch, d_parents,
+        parents_offset, d_child_metric, d_rest);
+    child_metric_near_kernel<DIM><<<grid_for(n, COOP_WAVES, 8192), 64 * COOP_WAVES, 0, st>>>(
+        g, knn->pts, knn->cell_start, knn->y, d_center, d_level, first, qw, k, reach, d_scratch, d_child_metric, d_rest, d_rest2);
+    S3_HIP_CHECK(hipMemsetAsync(d_rest, 0, 2 * sizeof(int32_t), st));
+    child_metric_far_kernel<DIM><<<grid_for(n * NCH, COOP_WAVES, 8192), 64 * COOP_WAVES, 0, st>>>(
+        g, knn->pts, knn->orig, knn->cell_start, knn->y, d_center, d_level, first, qw, k, reach, d_scratch, d_child_metric,
+        d_rest2, d_rest);
+    child_metric_rest_kernel<DIM><<<grid_for(n * NCH, KNN_BLOCK, 256), KNN_BLOCK, lds, st>>>(
+        g, knn->pts, knn->orig, knn->cell_start, knn->y, d_center, d_level, first, qw, k, d_scratch, d_child_metric, d_rest);
+    return S3_OK;
+}
+
 }  // namespace s3
 
 using namespace s3;
@@ -1734,13 +1567,12 @@ int s3_knn_create(const double *d_pts, int64_t n, int dim, double target_occupan
     }
     k->ncell = ncell;
 
-    int32_t *cid = nullptr, *cursor = nullptr, *block_sums = nullptr;
-    int64_t nscan = ncell + 1;
-    int64_t nblk = (nscan + 1023) / 1024;
+    int32_t *cid = nullptr, *cursor = nullptr, *scan_tmp = nullptr;
+    const int64_t nscan = ncell + 1;
     auto fail = [&](int rc) {
         if (cid) (void)hipFree(cid);
         if (cursor) (void)hipFree(cursor);
-        if (block_sums) (void)hipFree(block_sums);
+        if (scan_tmp) (void)hipFree(scan_tmp);
         s3_knn_destroy(k);
         return rc;
     };
@@ -1757,7 +1589,7 @@ int s3_knn_create(const double *d_pts, int64_t n, int dim, double target_occupan
     S3_TRY(hipMalloc(&k->cell_start, sizeof(int32_t) * nscan));
     S3_TRY(hipMalloc(&cid, sizeof(int32_t) * n));
     S3_TRY(hipMalloc(&cursor, sizeof(int32_t) * ncell));
-    S3_TRY(hipMalloc(&block_sums, sizeof(int32_t) * nblk));
+    S3_TRY(hipMalloc(&scan_tmp, sizeof(int32_t) * scan_tmp_items(nscan)));
     S3_TRY(hipMemsetAsync(k->cell_start, 0, sizeof(int32_t) * nscan, st));
     S3_TRY(hipMemsetAsync(cursor, 0, sizeof(int32_t) * ncell, st));
     if (dim == 2)
@@ -1765,10 +1597,7 @@ int s3_knn_create(const double *d_pts, int64_t n, int dim, double target_occupan
     else
         cell_count_kernel<3><<<grid_for(n, 256), 256, 0, st>>>(make_grid<3>(k), d_pts, n, cid, k->cell_start);
     S3_TRY(hipGetLastError());
-    scan_block_kernel<<<(unsigned)nblk, 256, 0, st>>>(k->cell_start, nscan, block_sums);
-    scan_sums_kernel<<<1, 256, 0, st>>>(block_sums, nblk);
-    scan_add_kernel<<<(unsigned)nblk, 256, 0, st>>>(k->cell_start, nscan, block_sums);
-    S3_TRY(hipGetLastError());
+    S3_TRY(exclusive_scan<int32_t>(k->cell_start, k->cell_start, nscan, scan_tmp, st));
     if (dim == 2)
         scatter_kernel<2><<<grid_for(n, 256), 256, 0, st>>>(d_pts, n, cid, k->cell_start, cursor, k->pts, k->orig);
     else
@@ -1777,17 +1606,17 @@ int s3_knn_create(const double *d_pts, int64_t n, int dim, double target_occupan
     S3_TRY(hipStreamSynchronize(st));
     (void)hipFree(cid);
     (void)hipFree(cursor);
-    (void)hipFree(block_sums);
+    (void)hipFree(scan_tmp);
 #undef S3_TRY
     // ---- second level: buckets with more than 8x the target occupancy get their own sub-lattice, so that strongly graded
     //      point clouds (boundary-layer meshes) do not degenerate into scanning thousands of points per bucket --------
     {
         const int split = (int)std::ceil(8.0 * occ);
-        int32_t *sub_size = nullptr, *bsum = nullptr, *sid = nullptr, *cur2 = nullptr, *orig2 = nullptr;
+        int32_t *sub_size = nullptr, *scan_tmp2 = nullptr, *sid = nullptr, *cur2 = nullptr, *orig2 = nullptr;
         double *pts2 = nullptr;
         unsigned long long *d_nref = nullptr;
         auto fail2 = [&](int rc) {
-            for (void *q : {(void *)sub_size, (void *)bsum, (void *)sid, (void *)cur2, (void *)orig2, (void *)pts2, (void *)d_nref})
+            for (void *q : {(void *)sub_size, (void *)scan_tmp2, (void *)sid, (void *)cur2, (void *)orig2, (void *)pts2, (void *)d_nref})
                 if (q) (void)hipFree(q);
             s3_knn_destroy(k);
             return rc;
@@ -1800,17 +1629,15 @@ int s3_knn_create(const double *d_pts, int64_t n, int dim, double target_occupan
             return fail2(_e == hipErrorOutOfMemory ? S3_ENOMEM : S3_EHIP);                             \
         }                                                                                              \
     } while (0)
-        const int64_t nscan2 = ncell + 1, nblk2 = (nscan2 + 1023) / 1024;
+        const int64_t nscan2 = ncell + 1;
         S3_TRY2(hipMalloc(&k->sub_res, ncell));
         S3_TRY2(hipMalloc(&sub_size, sizeof(int32_t) * nscan2));
-        S3_TRY2(hipMalloc(&bsum, sizeof(int32_t) * nblk2));
+        S3_TRY2(hipMalloc(&scan_tmp2, sizeof(int32_t) * scan_tmp_items(nscan2)));
         S3_TRY2(hipMalloc(&d_nref, sizeof(unsigned long long)));
         S3_TRY2(hipMemsetAsync(d_nref, 0, sizeof(unsigned long long), st));
         sub_plan_kernel<<<grid_for(nscan2, 256), 256, 0, st>>>(k->cell_start, ncell, split, occ, dim, k->sub_res, sub_size, d_nref);
-        scan_block_kernel<<<(unsigned)nblk2, 256, 0, st>>>(sub_size, nscan2, bsum);
-        scan_sums_kernel<<<1, 256, 0, st>>>(bsum, nblk2);
-        scan_add_kernel<<<(unsigned)nblk2, 256, 0, st>>>(sub_size, nscan2, bsum);
         S3_TRY2(hipGetLastError());
+        S3_TRY2(exclusive_scan<int32_t>(sub_size, sub_size, nscan2, scan_tmp2, st));
         unsigned long long nref = 0;
         int32_t pool = 0;
         S3_TRY2(hipMemcpyAsync(&nref, d_nref, sizeof(nref), hipMemcpyDeviceToHost, st));
@@ -1843,7 +1670,7 @@ int s3_knn_create(const double *d_pts, int64_t n, int dim, double target_occupan
             std::swap(k->pts, pts2);
             std::swap(k->orig, orig2);
         }
-        for (void *q : {(void *)bsum, (void *)sid, (void *)cur2, (void *)orig2, (void *)pts2, (void *)d_nref})
+        for (void *q : {(void *)scan_tmp2, (void *)sid, (void *)cur2, (void *)orig2, (void *)pts2, (void *)d_nref})
             if (q) (void)hipFree(q);
 #undef S3_TRY2
     }
@@ -1912,25 +1739,6 @@ int s3_idw_predict(const s3_knn *knn, const double *d_q, int64_t nq, int k, doub
     return S3_OK;
 }
 
-static bool knn_coop_enabled() {
-    const char *e = getenv("S3_KNN_COOP");
-    return !(e && e[0] == '0');
-}
-
-static int64_t knn_coop_min_cells() {
-    const char *e = getenv("S3_KNN_COOP_MIN");
-    return e ? atoll(e) : 1ll;
-}
-static bool knn_coop_forced() {
-    const char *e = getenv("S3_KNN_COOP");
-    return e && e[0] == '1';
-}
-
-static double knn_coop_margin() {
-    const char *e = getenv("S3_KNN_COOP_MARGIN");
-    return e ? atof(e) : 1.15;
-}
-
 static int child_gain_impl(const s3_knn *knn, int k, const double *d_center, const int32_t *d_level, int64_t first, int64_t n,
                            int dim, double width, const double *d_level_factor, double gain0, double *d_metric, double *d_gain,
                            double *d_scratch, const int32_t *d_parents, int64_t parents_offset, double *d_child_metric,
@@ -1944,64 +1752,20 @@ static int child_gain_impl(const s3_knn *knn, int k, const double *d_center, con
     S3_REQUIRE(d_parents == nullptr || d_child_metric != nullptr, "%s: parents given without the child-metric table", who);
     if (n == 0) return S3_OK;
     hipStream_t st = as_stream(stream);
-    size_t lds = knn_lds_bytes(k);
     const double qw = 0.25 * width;
-#define S3_CHILD_METRIC(DIM, REUSE, PER)                                                                                      \
-    child_metric_kernel<DIM, REUSE><<<grid_for(n * (PER), KNN_BLOCK), KNN_BLOCK, lds, st>>>(                                   \
-        make_grid<DIM>(knn), knn->pts, knn->orig, knn->cell_start, knn->y, d_center, d_level, first, n, qw, k, d_scratch,     \
-        d_parents, parents_offset, d_child_metric)
-#define S3_CHILD_COOP(DIM)                                                                                                    \
-    do {                                                                                                                      \
-    child_metric_coop_kernel<DIM><<<grid_for(n, COOP_WAVES), 64 * COOP_WAVES, 0, st>>>(                                       \
-        make_grid<DIM>(knn), knn->pts, knn->orig, knn->cell_start, knn->y, d_center, d_level, first, n, qw, k, reach,        \
-        d_scratch, d_parents, parents_offset, d_child_metric, d_rest);                                                        \
-    child_metric_near_kernel<DIM><<<grid_for(n, COOP_WAVES, 8192), 64 * COOP_WAVES, 0, st>>>(                                  \
-        make_grid<DIM>(knn), knn->pts, knn->cell_start, knn->y, d_center, d_level, first, qw, k, reach, d_scratch,            \
-        d_child_metric, d_rest, d_rest2);                                                                                     \
-    S3_HIP_CHECK(hipMemsetAsync(d_rest, 0, 2 * sizeof(int32_t), st));                                                         \
-    child_metric_far_kernel<DIM><<<grid_for(n * (1 << DIM), COOP_WAVES, 8192), 64 * COOP_WAVES, 0, st>>>(                      \
-        make_grid<DIM>(knn), knn->pts, knn->orig, knn->cell_start, knn->y, d_center, d_level, first, qw, k, reach, d_scratch, \
-        d_child_metric, d_rest2, d_rest);                                                                                     \
-    child_metric_rest_kernel<DIM><<<grid_for(n * (1 << DIM), KNN_BLOCK, 256), KNN_BLOCK, lds, st>>>(                           \
-        make_grid<DIM>(knn), knn->pts, knn->orig, knn->cell_start, knn->y, d_center, d_level, first, qw, k, d_scratch,        \
-        d_child_metric, d_rest);                                                                                              \
-    } while (0)
-    // The wavefront kernels (S3_KNN_COOP=0: the per-lane search for every child point, as for cells without a known parent):
-    //   coop -- one wavefront per cell, one shared box;  near -- what that leaves (cells too large for one box: the uniform
-    //   levels, the first adaptive batches), 2^dim queries per wavefront, each its own small box;  far -- what that leaves (next
-    //   to a body, at the edge of the cloud, outside it), one wavefront per query, boxes of growing size;  rest -- per lane.
-    // Measured on MI355X (rocprofv3 per launch): cylinder3D, adaptive batches of ~40 000 new cells: 0.37 + 0.08 + 0.21 ms against
-    // 1.16 ms for the per-lane kernel alone, the first adaptive batch 0.47 + 0.53 + 1.1 ms, the batches of the uniform levels
-    // 0.1 - 0.3 ms instead of 0.4 - 1.4 ms (a per-lane wavefront lives that long however few queries it has); refine
-    // 0.058 -> 0.050 s on one box.  box5e7, batches of ~230 000 fine cells: 3.8 - 4.2 + 0.5 - 1.1 + 0.05 ms against 7.0 ms,
-    // refine 0.70 -> 0.57 s.
-    const bool coop = d_parents != nullptr && knn_coop_enabled() && (n >= knn_coop_min_cells() || knn_coop_forced());
-    // how far (in bucket sides) the box reaches beyond the child points: the radius of the ball that holds k points at the
-    // index's average occupancy, plus a margin (S3_KNN_COOP_MARGIN, default 1.15); where the cloud is thinner than that the
-    // wavefront notices (fewer than k candidates inside its safe radius) and leaves the cell to the per-lane kernel
-    const double occupancy = (double)knn->n / (double)knn->ncell;
-    const double ball = dim == 3 ? std::cbrt(3.0 * k / (4.0 * 3.14159265358979323846 * occupancy))
-                                 : std::sqrt(k / (3.14159265358979323846 * occupancy));
-    const double reach = ball * knn_coop_margin();
-    // behind the n * (2^dim + 1) doubles of d_scratch: two lists (counter, pad, entries) that the kernels hand on in turns:
-    // coop -> rest -> near -> rest2 -> far -> rest (emptied in between) -> per-lane kernel
-    int32_t *d_rest = reinterpret_cast<int32_t *>(d_scratch + n * ((1 << dim) + 1));
-    int32_t *d_rest2 = d_rest + 2 + n * (1 << dim);
-    if (coop) {
-        S3_HIP_CHECK(hipMemsetAsync(d_rest, 0, 2 * sizeof(int32_t), st));
-        S3_HIP_CHECK(hipMemsetAsync(d_rest2, 0, 2 * sizeof(int32_t), st));
-    }
     if (dim == 2) {
-        if (coop) S3_CHILD_COOP(2); else if (d_parents) S3_CHILD_METRIC(2, true, 4); else S3_CHILD_METRIC(2, false, 5);
+        if (int rc = child_metric_launch<2>(knn, k, d_center, d_level, first, n, qw, d_scratch, d_parents, parents_offset,
+                                            d_child_metric, st))
+            return rc;
         child_gain_kernel<2><<<grid_for(n, 256), 256, 0, st>>>(d_scratch, d_level, first, n, d_level_factor, gain0,
                                                               d_metric, d_gain);
     } else {
-        if (coop) S3_CHILD_COOP(3); else if (d_parents) S3_CHILD_METRIC(3, true, 8); else S3_CHILD_METRIC(3, false, 9);
+        if (int rc = child_metric_launch<3>(knn, k, d_center, d_level, first, n, qw, d_scratch, d_parents, parents_offset,
+                                            d_child_metric, st))
+            return rc;
         child_gain_kernel<3><<<grid_for(n, 256), 256, 0, st>>>(d_scratch, d_level, first, n, d_level_factor, gain0,
                                                               d_metric, d_gain);
     }
-#undef S3_CHILD_METRIC
-#undef S3_CHILD_COOP
     S3_LAUNCH_CHECK();
     return S3_OK;
 }

@@ -1,7 +1,6 @@
 #!/bin/bash
 # GPU box: duration (µs) of every child_metric* launch, in launch order, of bench.py's refine of one workload
-# (rocprofv3 --kernel-trace) -> gpurun_out/knn_batches_<workload>.txt; and the refine wall-clock with the wavefront kernels
-# on (default) and off (S3_KNN_COOP=0), no profiler -> gpurun_out/knn_wall_<workload>.txt
+# (rocprofv3 --kernel-trace) -> knn_batches_<workload>.txt in the output directory below, and to stdout
 set -o pipefail
 w=${1:-cylinder3D_Re3900}
 root=$(pwd); out=$root/gpurun_out; mkdir -p "$out"; export TMPDIR=/tmp; cd /tmp
@@ -22,9 +21,4 @@ for r in rows:
 if line: print("  ".join(line))
 PY
 rm -rf "$out/kb_$w"
-cd "$root"
-for c in "" 0; do
-    S3_KNN_COOP=$c python3 bench.py --workload "$w" --no-cpu-baseline --no-batches --steps 2 --warmup 1 2>/dev/null \
-        | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('S3_KNN_COOP=%r' % '$c', d['refine_wall_s'], d['refine_runs_s'])" || exit 1
-done > "$out/knn_wall_$w.txt"
-cat "$out/knn_wall_$w.txt"
+cat "$out/knn_batches_$w.txt"
