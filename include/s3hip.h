@@ -275,6 +275,24 @@ int s3_interp_planned(s3_interp_plan *plan, const double *d_w /*[nc,k] or NULL*/
 int s3_interp_plan_set_source_ids(s3_interp_plan *plan, const int32_t *d_ids /*[n_src]*/, int64_t n_table_rows, s3_stream stream);
 int s3_interp_planned_src(s3_interp_plan *plan, const void *d_table, int dtype, int64_t n_table_rows, int64_t row_len,
                           int64_t in_stride, double *d_out /*[nc,row_len]*/, s3_stream stream);
+/* Which kernel s3_interp_planned (src = 0) or s3_interp_planned_src (src != 0) would launch for these rows; launches nothing.
+ * d_data is only looked at as an address.  h_out[5] = {route (S3_ROUTE_*), template width, EVEN, gy, tail}:
+ *   width  K (8 | 26) of the persistent kernel (the three STREAM routes), KQ (2 | 7 | 8) of SHORT_QUAD, KM (8 | 26 | 32) of
+ *          SHORT_REG; 0 for the others
+ *   EVEN   the persistent kernel's even-row-length form (row_len even); 0 for the other routes
+ *   gy     SHIFT / CHUNK*: workgroups that split the column chunks of a tile (1 = one workgroup per tile); 1 for the others
+ *   tail   SHIFT / CHUNK*: the last tiles of every XCD's share are cut into runs (tail map); 0 for the others */
+#define S3_ROUTE_STREAM_ELEM   1   /* persistent kernel, rows read with element alignment (not 16-byte aligned) */
+#define S3_ROUTE_STREAM_WIDE   2   /* persistent kernel, 16-byte aligned rows of 5 .. 24 chunks of 128 bytes */
+#define S3_ROUTE_STREAM_NARROW 3   /* persistent kernel, narrow layout: rows of two to four 16-byte vectors */
+#define S3_ROUTE_SHORT_QUAD    4   /* rows of four vectors, k <= 32: the lanes of a cell share its tables (DPP quad) */
+#define S3_ROUTE_SHORT_REG     5   /* rows of one to four vectors, k <= 32: weights in registers */
+#define S3_ROUTE_SHORT         6   /* rows of one to four vectors, any k: the generic short-row kernel */
+#define S3_ROUTE_SHIFT         7   /* 64-cell tiles, rows off the 128-byte grid: whole aligned lines per load */
+#define S3_ROUTE_CHUNK64       8   /* chunk kernel, 64-cell tiles */
+#define S3_ROUTE_CHUNK128      9   /* chunk kernel, 128-cell tiles */
+int s3_interp_plan_route(const s3_interp_plan *plan, int src, const void *d_data, int dtype, int64_t row_len, int64_t in_stride,
+                         int32_t *h_out /*[5]*/);
 
 /* ---- yardsticks of the measurement (bench.py's roofline line; no counterpart in the reference, not on any product path) ----
  * s3_yard_stream      a hand-written streaming kernel over d_src: every lane reads `reads` 16-byte vectors (coalesced) and

@@ -88,6 +88,7 @@ HIP_SIGNATURES = {
     "s3_interp_planned": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_vp]),
     "s3_interp_plan_set_source_ids": (c_int, [c_vp, c_vp, c_i64, c_vp]),
     "s3_interp_planned_src": (c_int, [c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "s3_interp_plan_route": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_i64, C.POINTER(c_i32)]),
     "s3_yard_stream": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, C.POINTER(c_i64), C.POINTER(c_i64)]),
     "s3_yard_plan_loads": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, C.POINTER(c_i64)]),
     "s3_comm_available": (c_int, []),

@@ -1237,9 +1237,20 @@ static int plan_schedule(s3_interp_plan *p, hipStream_t st) {
     return S3_OK;
 }
 
+// the kernel a planned launch takes (plan_route) and what it is launched with
+struct PlanRoute {
+    int route = 0;                       // S3_ROUTE_* (s3hip.h)
+    int width = 0;                       // template width: K of the persistent kernel, KQ of short_quad, KM of short_reg; 0 otherwise
+    int even = 0;                        // EVEN of the persistent kernel (even row length)
+    int gy = 1;                          // shift / chunk kernels: workgroups over the column chunks of a tile (1 = no split)
+    int tail = 0;                        // shift / chunk kernels: the tail map is used
+    int n_chunks = 0, chunks_per_block = 0, tail_tiles = 0, tail_split = 1;
+    int64_t n_wg = 0;                    // shift / chunk kernels: workgroups of the launch
+};
+
 template <typename T, bool ALIGNED, bool EVEN, bool NARROW = false>
 static int launch_stream_e(s3_interp_plan *p, const int32_t *rows, const void *data, int64_t row_len, int64_t in_stride,
-                           double *out, hipStream_t st) {
+                           double *out, int kk, hipStream_t st) {
     using LAY = std::conditional_t<NARROW, StreamLayoutNarrow, std::conditional_t<ALIGNED, StreamLayoutAligned, StreamLayoutUnaligned>>;
     constexpr int EPC = LAY::CHUNK_VECS * 16 / (int)sizeof(T);
     const int n_chunks = (int)((row_len + EPC - 1) / EPC);
@@ -1265,7 +1276,7 @@ static int launch_stream_e(s3_interp_plan *p, const int32_t *rows, const void *d
                                                             p->wl, static_cast<const T *>(data), row_len, in_stride,           \
                                                             out, p->dump, p->sched_begin, p->sched_desc, n_chunks);           \
     } while (0)
-    if (p->k == 8) S3_LAUNCH_STREAM(8);
+    if (kk == 8) S3_LAUNCH_STREAM(8);
     else S3_LAUNCH_STREAM(26);
 #undef S3_LAUNCH_STREAM
     S3_LAUNCH_CHECK();
@@ -1274,20 +1285,26 @@ static int launch_stream_e(s3_interp_plan *p, const int32_t *rows, const void *d
 
 template <typename T, bool ALIGNED, bool NARROW = false>
 static int launch_stream(s3_interp_plan *p, const int32_t *rows, const void *data, int64_t row_len, int64_t in_stride,
-                         double *out, hipStream_t st) {
-    if (row_len & 1) return launch_stream_e<T, ALIGNED, false, NARROW>(p, rows, data, row_len, in_stride, out, st);
-    return launch_stream_e<T, ALIGNED, true, NARROW>(p, rows, data, row_len, in_stride, out, st);
+                         double *out, const PlanRoute &r, hipStream_t st) {
+    if (!r.even) return launch_stream_e<T, ALIGNED, false, NARROW>(p, rows, data, row_len, in_stride, out, r.width, st);
+    return launch_stream_e<T, ALIGNED, true, NARROW>(p, rows, data, row_len, in_stride, out, r.width, st);
 }
 
-template <typename T>
-static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows, bool aligned, const void *data, int64_t row_len,
-                          int64_t in_stride, double *out, hipStream_t st) {
+// Which kernel a planned launch takes, and with which template width and grid: decided here and nowhere else --
+// launch_planned launches from the result and s3_interp_plan_route reports it, so the two cannot drift apart.  Host only:
+// `data` is an address, never dereferenced.  `elem` = bytes per element of the rows (4 | 8).
+static int plan_route(const s3_interp_plan *p, const int32_t *rows, int64_t n_rows, bool aligned, const void *data, int64_t row_len,
+                      int64_t in_stride, int elem, PlanRoute &r) {
+    r = PlanRoute();
+    r.even = (row_len & 1) == 0;
     if (!aligned) {                              // element-aligned rows read where they lie: the persistent kernel only
         S3_REQUIRE(stream_can_take(p), "s3_interp_planned: rows that are not 16-byte aligned need k = 8 | 26 and 64-cell tiles");
-        return launch_stream<T, false>(p, rows, data, row_len, in_stride, out, st);
+        r.route = S3_ROUTE_STREAM_ELEM;
+        r.width = p->k;
+        return S3_OK;
     }
-    constexpr int EPC = PL_SEG / (int)sizeof(T);
-    constexpr int EPV = 16 / (int)sizeof(T);
+    const int EPC = PL_SEG / elem;
+    const int EPV = 16 / elem;
     const int n_chunks = (int)((row_len + EPC - 1) / EPC);
     const int vpr = (int)((row_len + EPV - 1) / EPV);           // 16-byte vectors per row
     const int64_t tiles_per_xcd = (p->n_tiles + 7) / 8;
@@ -1298,63 +1315,38 @@ static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows
     // aligned lines (interp_planned_shift_kernel, below) than with the persistent kernel's straddling segments: 800-byte rows 0.850
     // against 0.906 ms, 400-byte rows 0.529 / 0.553, 272-byte rows 0.414 / 0.424 (cylinder3D grid, interleaved in one process,
     // HISTORY 5.1b)
-    const bool off_line = reinterpret_cast<uintptr_t>(data) % PL_SEG != 0 || ((uint64_t)in_stride * sizeof(T)) % PL_SEG != 0;
+    const bool off_line = reinterpret_cast<uintptr_t>(data) % PL_SEG != 0 || ((uint64_t)in_stride * elem) % PL_SEG != 0;
     const bool shift = p->tc == 64 && off_line;
-    if (vpr > SHORT_ROW_VECS && n_chunks <= STREAM_MAX_CHUNKS && stream_ok && !(shift && n_chunks >= SHIFT_MIN_CHUNKS))
-        return launch_stream<T, true>(p, rows, data, row_len, in_stride, out, st);
+    if (vpr > SHORT_ROW_VECS && n_chunks <= STREAM_MAX_CHUNKS && stream_ok && !(shift && n_chunks >= SHIFT_MIN_CHUNKS)) {
+        r.route = S3_ROUTE_STREAM_WIDE;
+        r.width = p->k;
+        return S3_OK;
+    }
     // (r4) rows of two to four vectors (5 .. 16 fp32 snapshots): the persistent kernel in its narrow layout -- four lanes per row,
     // eight gathers per lane and step -- unless the table is a large one read in place.  Measured, one box each: cylinder3D, 16 / 12
     // snapshots, pitched copy 0.089 / 0.088 ms against 0.105 / 0.117 with the short-row kernels, read in place (320-MB table) 0.100 /
     // 0.116 against 0.112 / 0.121; box5e7 (10 M cells, 16 snapshots) pitched copy 1.745 against 1.786 ms, but its 3.2-GB table read in
     // place 2.363 against 2.208: there five short-lived workgroups per CU hide the page-table walks of a scattered table better
     // than two persistent ones.  Rows of one vector stay with the short-row kernels (0.096 against 0.078 ms).
-    const bool big_table = rows != p->rows && (uint64_t)n_rows * (uint64_t)in_stride * sizeof(T) > ((uint64_t)1 << 30);
-    if (vpr >= 2 && vpr <= 4 && !big_table && stream_ok)
-        return launch_stream<T, true, true>(p, rows, data, row_len, in_stride, out, st);
+    const bool big_table = rows != p->rows && (uint64_t)n_rows * (uint64_t)in_stride * elem > ((uint64_t)1 << 30);
+    if (vpr >= 2 && vpr <= 4 && !big_table && stream_ok) {
+        r.route = S3_ROUTE_STREAM_NARROW;
+        r.width = p->k;
+        return S3_OK;
+    }
+    r.even = 0;                                  // (a template parameter of the persistent kernel only)
     if (vpr <= SHORT_ROW_VECS && p->tc == 64) {
         if (vpr == 4 && p->ucap * vpr <= 256 * 8 && p->k <= 32) {
             // four vectors per row: the lanes of a cell are a DPP quad and share the loads of its weights / positions
-            const size_t lds = (size_t)p->ucap * vpr * 16;
-#define S3_LAUNCH_SHORT_QUAD(KQ)                                                                                                 \
-    do {                                                                                                                         \
-        auto kern = interp_planned_short_quad_kernel<T, KQ>;                                                                     \
-        kern<<<dim3((unsigned)gx), 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, \
-                                                   static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles,            \
-                                                   tiles_per_xcd);                                                               \
-    } while (0)
-            if (p->k <= 8) S3_LAUNCH_SHORT_QUAD(2);
-            else if (p->k <= 28) S3_LAUNCH_SHORT_QUAD(7);
-            else S3_LAUNCH_SHORT_QUAD(8);
-#undef S3_LAUNCH_SHORT_QUAD
-            S3_LAUNCH_CHECK();
-            return S3_OK;
-        }
-        if (vpr <= 4 && p->ucap * vpr <= 256 * 8 && p->k <= 32) {
+            r.route = S3_ROUTE_SHORT_QUAD;
+            r.width = p->k <= 8 ? 2 : p->k <= 28 ? 7 : 8;
+        } else if (vpr <= 4 && p->ucap * vpr <= 256 * 8 && p->k <= 32) {
             // one lane per (cell, vector) pair, weights in registers
-            const size_t lds = (size_t)p->ucap * vpr * 16;
-#define S3_LAUNCH_SHORT_REG(KM)                                                                                                  \
-    do {                                                                                                                         \
-        auto kern = interp_planned_short_reg_kernel<T, KM>;                                                                      \
-        kern<<<dim3((unsigned)gx), 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, \
-                                                   static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles,            \
-                                                   tiles_per_xcd, vpr);                                                          \
-    } while (0)
-            if (p->k <= 8) S3_LAUNCH_SHORT_REG(8);
-            else if (p->k <= 26) S3_LAUNCH_SHORT_REG(26);
-            else S3_LAUNCH_SHORT_REG(32);
-#undef S3_LAUNCH_SHORT_REG
-            S3_LAUNCH_CHECK();
-            return S3_OK;
+            r.route = S3_ROUTE_SHORT_REG;
+            r.width = p->k <= 8 ? 8 : p->k <= 26 ? 26 : 32;
+        } else {
+            r.route = S3_ROUTE_SHORT;
         }
-        const int pitch = vpr < 8 ? vpr : 8;
-        const size_t lds = (size_t)p->ucap * pitch * 16 + (size_t)p->k * p->tc * (sizeof(double) + sizeof(uint16_t)) +
-                           (size_t)p->tc * sizeof(int32_t);
-        auto kern = interp_planned_short_kernel<T, 64>;
-        S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        kern<<<dim3((unsigned)gx), 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k,
-                                                   p->ucap, static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles,
-                                                   tiles_per_xcd, vpr, pitch);
-        S3_LAUNCH_CHECK();
         return S3_OK;
     }
     // The column chunks of a tile are split into runs over several workgroups when there are too few tiles to fill the chip
@@ -1374,37 +1366,104 @@ static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows
     const int tail = use_tail ? TAIL_TILES : 0, tail_split = use_tail ? TAIL_RUNS : 1;
     const int64_t n_wg = use_tail ? 8 * (tiles_per_xcd + (int64_t)tail * (tail_split - 1)) : gx * gy;
     S3_REQUIRE(n_wg < ((int64_t)1 << 31), "s3_interp_planned: too many workgroups");
-    const size_t lds = (size_t)p->ucap * PL_SEG + (size_t)p->k * p->tc * (sizeof(double) + sizeof(uint16_t));
-    dim3 grid((unsigned)n_wg);
     // rows that do not start on 128-byte boundaries (a dense batch read where it lies): whole aligned lines per load, the
     // per-row phase undone on the way into LDS.
+    r.route = shift ? S3_ROUTE_SHIFT : p->tc == 128 ? S3_ROUTE_CHUNK128 : S3_ROUTE_CHUNK64;
+    r.gy = gy;
+    r.tail = use_tail;
+    r.n_chunks = n_chunks;
+    r.chunks_per_block = chunks_per_block;
+    r.tail_tiles = tail;
+    r.tail_split = tail_split;
+    r.n_wg = n_wg;
+    return S3_OK;
+}
+
+template <typename T>
+static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows, bool aligned, const void *data, int64_t row_len,
+                          int64_t in_stride, double *out, hipStream_t st) {
+    PlanRoute r;
+    const int rc = plan_route(p, rows, n_rows, aligned, data, row_len, in_stride, (int)sizeof(T), r);
+    if (rc != S3_OK) return rc;
+    if (r.route == S3_ROUTE_STREAM_ELEM) return launch_stream<T, false>(p, rows, data, row_len, in_stride, out, r, st);
+    if (r.route == S3_ROUTE_STREAM_WIDE) return launch_stream<T, true>(p, rows, data, row_len, in_stride, out, r, st);
+    if (r.route == S3_ROUTE_STREAM_NARROW) return launch_stream<T, true, true>(p, rows, data, row_len, in_stride, out, r, st);
+    const int vpr = (int)((row_len + 16 / (int)sizeof(T) - 1) / (16 / (int)sizeof(T)));
+    const int64_t tiles_per_xcd = (p->n_tiles + 7) / 8;
+    const int64_t gx = tiles_per_xcd * 8;
+    if (r.route == S3_ROUTE_SHORT_QUAD) {
+        const size_t lds = (size_t)p->ucap * vpr * 16;
+#define S3_LAUNCH_SHORT_QUAD(KQ)                                                                                                 \
+    do {                                                                                                                         \
+        auto kern = interp_planned_short_quad_kernel<T, KQ>;                                                                     \
+        kern<<<dim3((unsigned)gx), 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, \
+                                                   static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles,            \
+                                                   tiles_per_xcd);                                                               \
+    } while (0)
+        if (r.width == 2) S3_LAUNCH_SHORT_QUAD(2);
+        else if (r.width == 7) S3_LAUNCH_SHORT_QUAD(7);
+        else S3_LAUNCH_SHORT_QUAD(8);
+#undef S3_LAUNCH_SHORT_QUAD
+        S3_LAUNCH_CHECK();
+        return S3_OK;
+    }
+    if (r.route == S3_ROUTE_SHORT_REG) {
+        const size_t lds = (size_t)p->ucap * vpr * 16;
+#define S3_LAUNCH_SHORT_REG(KM)                                                                                                  \
+    do {                                                                                                                         \
+        auto kern = interp_planned_short_reg_kernel<T, KM>;                                                                      \
+        kern<<<dim3((unsigned)gx), 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, \
+                                                   static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles,            \
+                                                   tiles_per_xcd, vpr);                                                          \
+    } while (0)
+        if (r.width == 8) S3_LAUNCH_SHORT_REG(8);
+        else if (r.width == 26) S3_LAUNCH_SHORT_REG(26);
+        else S3_LAUNCH_SHORT_REG(32);
+#undef S3_LAUNCH_SHORT_REG
+        S3_LAUNCH_CHECK();
+        return S3_OK;
+    }
+    if (r.route == S3_ROUTE_SHORT) {
+        const int pitch = vpr < 8 ? vpr : 8;
+        const size_t lds = (size_t)p->ucap * pitch * 16 + (size_t)p->k * p->tc * (sizeof(double) + sizeof(uint16_t)) +
+                           (size_t)p->tc * sizeof(int32_t);
+        auto kern = interp_planned_short_kernel<T, 64>;
+        S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        kern<<<dim3((unsigned)gx), 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k,
+                                                   p->ucap, static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles,
+                                                   tiles_per_xcd, vpr, pitch);
+        S3_LAUNCH_CHECK();
+        return S3_OK;
+    }
+    const size_t lds = (size_t)p->ucap * PL_SEG + (size_t)p->k * p->tc * (sizeof(double) + sizeof(uint16_t));
+    dim3 grid((unsigned)r.n_wg);
     // (r5) Whole-line output stores -- a cell whose output row starts 64 bytes into a line holds the last 64 bytes of a step back
     // for one step -- were built and not kept.  They bring WRITE_SIZE down to the output's size (3.955 -> 3.690 GB per launch at
     // 1000 snapshots, traffic 1.31 -> 1.29 x algorithmic) but cost the launch 0.2-0.9 % (3.564 against 3.531 ms, 3.488 / 3.456,
     // 3.575 / 3.569 on three boxes, interleaved in one process): the counter tallies two partial write-backs of a line as more than
     // the line, the DRAM bursts are the same, and the divergent store path is not free.  (A form with ONE store sequence for all
     // lanes behind selects: 3.588 ms -- worse than the branch.)  HISTORY 5.1b.
-    if (shift) {
+    if (r.route == S3_ROUTE_SHIFT) {
         auto kern = interp_planned_shift_kernel<T>;
         S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         kern<<<grid, 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,
                                      static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles, tiles_per_xcd,
-                                     chunks_per_block, n_chunks, tail, tail_split);
+                                     r.chunks_per_block, r.n_chunks, r.tail_tiles, r.tail_split);
         S3_LAUNCH_CHECK();
         return S3_OK;
     }
-    if (p->tc == 128) {
+    if (r.route == S3_ROUTE_CHUNK128) {
         auto kern = interp_planned_kernel<T, 128>;
         S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         kern<<<grid, 512, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,
                                      static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles, tiles_per_xcd,
-                                     chunks_per_block, n_chunks, tail, tail_split);
+                                     r.chunks_per_block, r.n_chunks, r.tail_tiles, r.tail_split);
     } else {
         auto kern = interp_planned_kernel<T, 64>;
         S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         kern<<<grid, 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,
                                      static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles, tiles_per_xcd,
-                                     chunks_per_block, n_chunks, tail, tail_split);
+                                     r.chunks_per_block, r.n_chunks, r.tail_tiles, r.tail_split);
     }
     S3_LAUNCH_CHECK();
     return S3_OK;
@@ -1648,6 +1707,28 @@ int s3_interp_plan_set_weights(s3_interp_plan *p, const double *d_w, s3_stream s
     return S3_OK;
 }
 
+// the source-row layout of a launch (row_len >= 1, d_data non-null): `in_stride` resolved, `aligned` = the rows are read as
+// whole 16-byte vectors (false: element alignment, the persistent kernel)
+static int planned_layout(const s3_interp_plan *p, const char *who, const void *d_data, int dtype, int64_t row_len, int64_t &in_stride,
+                          bool &aligned) {
+    const int epv = dtype == S3_DTYPE_F32 ? 4 : 2;
+    const uintptr_t a_in = reinterpret_cast<uintptr_t>(d_data);
+    if (in_stride <= 0) in_stride = row_len;
+    S3_REQUIRE(in_stride >= row_len && in_stride < ((int64_t)1 << 31), "%s: in_stride %lld < row_len %lld (or >= 2^31)", who,
+               (long long)in_stride, (long long)row_len);
+    // pitched rows: every source row starts on a 16-byte boundary and is readable up to the next multiple of 16 bytes (the
+    // ragged tail of a row is loaded as a whole vector, the surplus lanes are never stored).  Anything else -- a dense
+    // [N, n_comp * T] batch read where it lies -- is read with element alignment by the persistent kernel, which touches
+    // nothing beyond the end of a row; it wants rows of at least one 16-byte vector.
+    aligned = in_stride % epv == 0 && in_stride >= (row_len + epv - 1) / epv * epv && a_in % 16 == 0;
+    if (!aligned)
+        S3_REQUIRE(a_in % (16 / epv) == 0 && row_len >= epv && stream_can_take(p),
+                   "%s: source rows must be 16-byte aligned with a pitch >= the row length rounded up to %d elements, or "
+                   "element-aligned rows of >= %d elements on a plan with k = 8 | 26 (row_len %lld, in_stride %lld)", who, epv, epv,
+                   (long long)row_len, (long long)in_stride);
+    return S3_OK;
+}
+
 // common part of the two launches: `rows` = the plan's row list in the numbering of d_data's rows
 static int planned_dispatch(s3_interp_plan *p, const int32_t *rows, int64_t n_rows, const char *who, const void *d_data, int dtype,
                             int64_t row_len, int64_t in_stride, double *d_out, s3_stream stream) {
@@ -1656,21 +1737,10 @@ static int planned_dispatch(s3_interp_plan *p, const int32_t *rows, int64_t n_ro
     S3_REQUIRE(row_len >= 0, "%s: bad row_len", who);
     if (row_len == 0) return S3_OK;
     S3_REQUIRE(d_data && d_out, "%s: null array", who);
-    const int epv = dtype == S3_DTYPE_F32 ? 4 : 2;
-    const uintptr_t a_in = reinterpret_cast<uintptr_t>(d_data), a_out = reinterpret_cast<uintptr_t>(d_out);
-    if (in_stride <= 0) in_stride = row_len;
-    S3_REQUIRE(in_stride >= row_len && in_stride < ((int64_t)1 << 31), "%s: in_stride %lld < row_len %lld (or >= 2^31)", who,
-               (long long)in_stride, (long long)row_len);
-    // pitched rows: every source row starts on a 16-byte boundary and is readable up to the next multiple of 16 bytes (the
-    // ragged tail of a row is loaded as a whole vector, the surplus lanes are never stored).  Anything else -- a dense
-    // [N, n_comp * T] batch read where it lies -- is read with element alignment by the persistent kernel, which touches
-    // nothing beyond the end of a row; it wants rows of at least one 16-byte vector.
-    const bool aligned = in_stride % epv == 0 && in_stride >= (row_len + epv - 1) / epv * epv && a_in % 16 == 0;
-    if (!aligned)
-        S3_REQUIRE(a_in % (16 / epv) == 0 && row_len >= epv && stream_can_take(p),
-                   "%s: source rows must be 16-byte aligned with a pitch >= the row length rounded up to %d elements, or "
-                   "element-aligned rows of >= %d elements on a plan with k = 8 | 26 (row_len %lld, in_stride %lld)", who, epv, epv,
-                   (long long)row_len, (long long)in_stride);
+    bool aligned = false;
+    const int rc = planned_layout(p, who, d_data, dtype, row_len, in_stride, aligned);
+    if (rc != S3_OK) return rc;
+    const uintptr_t a_out = reinterpret_cast<uintptr_t>(d_out);
     // output rows start on 8-byte boundaries (pairs are written with element alignment where the row length is odd)
     S3_REQUIRE(a_out % ((row_len & 1) ? 8 : 16) == 0, "%s: output not aligned (row_len %lld)", who, (long long)row_len);
     if (dtype == S3_DTYPE_F32) return launch_planned<float>(p, rows, n_rows, aligned, d_data, row_len, in_stride, d_out, as_stream(stream));
@@ -1727,6 +1797,27 @@ int s3_interp_planned_src(s3_interp_plan *p, const void *d_table, int dtype, int
     S3_REQUIRE(n_table_rows == p->n_table, "s3_interp_planned_src: the table has %lld rows, the ids were given for %lld",
                (long long)n_table_rows, (long long)p->n_table);
     return planned_dispatch(p, p->rows_src, p->n_table, "s3_interp_planned_src", d_table, dtype, row_len, in_stride, d_out, stream);
+}
+
+int s3_interp_plan_route(const s3_interp_plan *p, int src, const void *d_data, int dtype, int64_t row_len, int64_t in_stride,
+                         int32_t *h_out) {
+    S3_REQUIRE(p != nullptr && h_out != nullptr, "s3_interp_plan_route: null argument");
+    S3_REQUIRE(dtype == S3_DTYPE_F32 || dtype == S3_DTYPE_F64, "s3_interp_plan_route: unknown dtype %d", dtype);
+    S3_REQUIRE(row_len >= 1 && d_data != nullptr, "s3_interp_plan_route: no rows (a launch with row_len 0 does nothing)");
+    S3_REQUIRE(!src || (p->rows_src != nullptr && p->n_table > 0), "s3_interp_plan_route: call s3_interp_plan_set_source_ids first");
+    bool aligned = false;
+    int rc = planned_layout(p, "s3_interp_plan_route", d_data, dtype, row_len, in_stride, aligned);
+    if (rc != S3_OK) return rc;
+    PlanRoute r;
+    rc = plan_route(p, src ? p->rows_src : p->rows, src ? p->n_table : p->n_src, aligned, d_data, row_len, in_stride,
+                    dtype == S3_DTYPE_F32 ? 4 : 8, r);
+    if (rc != S3_OK) return rc;
+    h_out[0] = r.route;
+    h_out[1] = r.width;
+    h_out[2] = r.even;
+    h_out[3] = r.gy;
+    h_out[4] = r.tail;
+    return S3_OK;
 }
 
 

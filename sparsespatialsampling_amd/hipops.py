@@ -337,6 +337,23 @@ class InterpPlan:
             raise TypeError(f"InterpPlan.{who}: device tensors required, out must be contiguous float64 [nc, ...]")
         return row_len, in_stride, out
 
+    ROUTES = {1: "stream_elem", 2: "stream_wide", 3: "stream_narrow", 4: "short_quad", 5: "short_reg", 6: "short", 7: "shift",
+              8: "chunk64", 9: "chunk128"}             # S3_ROUTE_* (s3hip.h)
+
+    def route(self, data, src=False):
+        """the kernel ``interp(w, data)`` (``src``: ``interp_src(data)``) would launch, and how (s3_interp_plan_route; launches
+        nothing) -> dict(route=<name>, width=<template width>, even=, gy=, tail=)"""
+        layout = self._layout(data, self.k)
+        if layout is None or not data.is_cuda:
+            raise TypeError("InterpPlan.route: the planned kernels cannot read these rows (see interp)")
+        if src and self.n_table is None:
+            raise RuntimeError("InterpPlan.route: call set_source_ids first")
+        row_len, in_stride = layout
+        h = (C.c_int32 * 5)()
+        check(_lib.hip_lib().s3_interp_plan_route(self._handle, int(bool(src)), C.c_void_p(data.data_ptr()), DTYPE_CODE[data.dtype],
+                                                  row_len, in_stride, h), "s3_interp_plan_route")
+        return dict(route=self.ROUTES[h[0]], width=h[1], even=h[2], gy=h[3], tail=h[4])
+
     def yard_loads(self, table, variant=0, in_place=True):
         """yardstick (bench.py): the loads of this plan on ``table`` and nothing else (s3_yard_plan_loads); -> staged bytes"""
         row_len, in_stride = self._layout(table, None)
