@@ -140,7 +140,11 @@ int s3_child_gain(const s3_knn *knn, int k, const double *d_center, const int32_
  * csrc/knn.hip); the queries that scheme cannot answer are listed behind the doubles and handed on: to a grouped search
  * (2^dim queries per wavefront, each its own small box: cells too large for one box), then to one wavefront per query
  * (next to a body, at the edge of the cloud, outside it), and what is still left (refined buckets, ties in distance, k > 48)
- * to the per-lane search.  Same bits whichever kernel answers. */
+ * to the per-lane search.  Same bits whichever kernel answers.
+ * After a call with d_parents, the int32 words behind the n*(2^dim+1) doubles of d_scratch (R = that address, L = 2 + n*2^dim)
+ * hold the hand-off counts, in child points: R[L+1] = what the per-cell wavefronts left to the grouped search, R[L] = what the
+ * grouped search left to the one-wavefront-per-query search, R[0] = what that left to the per-lane search.  Without d_parents
+ * these words are not touched. */
 int s3_child_gain_reuse(const s3_knn *knn, int k, const double *d_center, const int32_t *d_level, int64_t first, int64_t n,
                         int dim, double width, const double *d_level_factor, double gain0, double *d_metric /*[cap]*/,
                         double *d_gain /*[cap]*/, double *d_scratch, const int32_t *d_parents /*or NULL*/,

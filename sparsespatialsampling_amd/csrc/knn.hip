@@ -1482,7 +1482,8 @@ static int child_metric_launch(const s3_knn *knn, int k, const double *d_center,
                                  : std::sqrt(k / (3.14159265358979323846 * occupancy));
     const double reach = ball * COOP_MARGIN;
     // behind the n * (2^dim + 1) doubles of d_scratch: two lists (counter, pad, entries) that the kernels hand on in turns:
-    // coop -> rest -> near -> rest2 -> far -> rest (emptied in between) -> per-lane kernel
+    // coop -> rest -> near -> rest2 -> far -> rest (emptied in between) -> per-lane kernel.  No kernel reads the pad words: coop's
+    // count is kept in rest2's before rest is emptied, so that the three hand-off counts can be read afterwards (s3hip.h)
     int32_t *d_rest = reinterpret_cast<int32_t *>(d_scratch + n * (NCH + 1));
     int32_t *d_rest2 = d_rest + 2 + n * NCH;
     S3_HIP_CHECK(hipMemsetAsync(d_rest, 0, 2 * sizeof(int32_t), st));
@@ -1492,6 +1493,7 @@ static int child_metric_launch(const s3_knn *knn, int k, const double *d_center,
         parents_offset, d_child_metric, d_rest);
     child_metric_near_kernel<DIM><<<grid_for(n, COOP_WAVES, 8192), 64 * COOP_WAVES, 0, st>>>(
         g, knn->pts, knn->cell_start, knn->y, d_center, d_level, first, qw, k, reach, d_scratch, d_child_metric, d_rest, d_rest2);
+    S3_HIP_CHECK(hipMemcpyAsync(d_rest2 + 1, d_rest, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     S3_HIP_CHECK(hipMemsetAsync(d_rest, 0, 2 * sizeof(int32_t), st));
     child_metric_far_kernel<DIM><<<grid_for(n * NCH, COOP_WAVES, 8192), 64 * COOP_WAVES, 0, st>>>(
         g, knn->pts, knn->orig, knn->cell_start, knn->y, d_center, d_level, first, qw, k, reach, d_scratch, d_child_metric,

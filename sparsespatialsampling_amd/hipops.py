@@ -563,6 +563,17 @@ def child_gain_reuse(knn, k, center, level, first, n, width, level_factor, gain0
           "s3_child_gain_reuse")
 
 
+def child_gain_handoffs(scratch, n, dim):
+    """the hand-off counts a ``child_gain_reuse`` call with ``parents`` over ``n`` cells left in its ``scratch`` (include/s3hip.h),
+    in child points: (left by the per-cell wavefronts, left by the grouped search, left by the one-wavefront-per-query search
+    to the per-lane search)"""
+    nch = 2 ** int(dim)
+    at = n * (nch + 1)                                      # the two lists: (counter, pad, n * 2^dim entries) int32 each
+    rest = to_host(scratch[at:at + 1]).view(np.int32)
+    rest2 = to_host(scratch[at + 1 + n * nch // 2:at + 2 + n * nch // 2]).view(np.int32)
+    return int(rest2[1]), int(rest2[0]), int(rest[0])
+
+
 def mask_box(center, level, cells, first, n, width, lo, hi, refine_mode, keep_inside, invalid):
     dim = int(center.shape[1])
     lo, hi = _host_f64(lo), _host_f64(hi)
