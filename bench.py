@@ -3,7 +3,13 @@
 bench.py -- S^3 hot path on MI355X: snapshot interpolation throughput (+ refine wall-clock) on the synthetic
 cylinder3D_Re3900 workload of BASELINE.json / SURVEY.md 8(d).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline needs and no more: it builds the workload and its grid (one `refine()`), the KNN cache and
+the snapshot batch, runs the W warm-up and K timed steps, writes the outputs of `--dump-outputs` and prints the JSON line.
+Everything else below -- the refine wall-clock (four more grid generations), the traffic measured by profiler child passes, the
+yardsticks, the other batch shapes and layouts, the transport legs, the CPU baselines, the grid digest, the export leg of N > 1
+and the rest of `compute_svd` for `--workload svd` -- runs with `--full` only.
 
 A *step* is one pass of the interpolation hot path over one batch of synthetic snapshots already resident in HBM IN THE FORM
 THE API RECEIVES IT (interpolate_data(w, idx, data), reference export.py:446-468): a dense tensor [N_points, T_batch] fp32 with
@@ -11,9 +17,9 @@ a row for every point of the CFD mesh, read where it lies through ExportData's c
 (s3_interp_planned_src) -> out [N_cells, T_batch] f64 in HBM.  The same launch on a pre-compacted, pitched copy of the
 referenced rows (the layout ExportData uploads HOST batches into; the headline of rounds 1-3) is the sub-record
 `roofline.pitched_copy`.
-The grid comes from `SamplingTree.refine()` run on the GPU(s) before the timed region; its wall-clock is reported as
-`refine_wall_s` in the same JSON line (second of two runs; the first one of a process, which also pays for the device
-allocations, is `refine_first_run_wall_s`).
+The grid comes from `SamplingTree.refine()` run on the GPU(s) before the timed region; with `--full` its wall-clock is reported
+as `refine_wall_s` in the same JSON line (median of the last three of four runs; the first one of a process, which also pays for
+the device allocations, is `refine_first_run_wall_s`).
 
 Multi-GPU (one process per GPU; the collectives run inside libs3hip.so on RCCL).  Under `torch.distributed.run` (WORLD_SIZE ==
 --gpus) every rank runs main(); WITHOUT a launcher `python bench.py --gpus N` becomes the parent of N fresh ranks itself
@@ -33,7 +39,7 @@ DIR/<name>.npy (dump_outputs: at most 64 MB; a fixed, seeded sample of the rows 
 seeded, so two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP events on the launch stream: mean, min, median, max
-per launch, and the identity of the device they were taken on) and, at N = 1:
+per launch, and the identity of the device they were taken on) and, with `--full` at N = 1:
 * `roofline_batches`: the same kernel family at the batch lengths the reference actually exports with -- 25 snapshots of a
   scalar (100-byte ragged rows) and of a 3-component field (300-byte rows), examples/s3_for_cylinder3D_Re3900.py:28-69 ->
   utils.py:204-226, and 100 snapshots -- each with its own algorithmic bytes;
@@ -677,7 +683,8 @@ def bench_svd(args, json_fd):
     against AMD's datasheet peak for f64 matrix operations (78.6 TFLOP/s; the guide lists none) and against the rate a bare
     loop of the same instruction sustains on this pool (46 TFLOP/s, tools/mfma_f64_peak.hip).  Eigen-solve and mode GEMM of
     compute_svd: the eigen-solve of the T x T matrix is a vendor-library call (rocSOLVER's dsyevd behind s3_sym_eig), the mode GEMM is
-    s3_centered_gemm on the same matrix cores (`mode_gemm`); the whole call is timed in `compute_svd_s`, not in `value`."""
+    s3_centered_gemm on the same matrix cores (`mode_gemm`); the whole call is timed in `compute_svd_s`, not in `value` (both with
+    `--full` only: svd_extras)."""
     from sparsespatialsampling_amd import svd, metrics
     n, t = 461_130, args.t_batch or 1000
     gen = pt.Generator(device="cuda").manual_seed(7)
@@ -697,6 +704,26 @@ def bench_svd(args, json_fd):
     del gram
     flops = float(n) * t * (t + 1)
     st = ms_stats(ms)
+    achieved = flops / (st["kernel_ms"] * 1e-3) / 1e12
+    res = {"metric": "TFLOP/s weighted Gram matrix (f64 matrix cores)", "value": flops * args.steps / elapsed / 1e12, "unit": "TFLOP/s",
+           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
+           "config": {"workload": f"svd: weighted Gram matrix of {n} cells x {t} snapshots f64 (the bench grid's interpolated field)",
+                      "n_cells": n, "t_batch": t},
+           "device": device_identity(),
+           "roofline": {"bound": "mfma", "achieved": achieved, "peak": 78.6, "unit": "TFLOP/s", "frac": achieved / 78.6,
+                        "peak_source": "AMD MI355X datasheet, f64 matrix (the CDNA4 guide lists no f64 figure)",
+                        "sustained_instruction_rate": 46.0, "frac_of_sustained": achieved / 46.0,
+                        "sustained_source": "bare v_mfma_f64_16x16x4_f64 loop, operands in registers (tools/mfma_f64_peak.hip, HISTORY 5.6)",
+                        "kernel": "gram_block_kernel", "algorithmic_flops": flops, "traffic": None, **st}}
+    if args.full:
+        res.update(svd_extras(x, mean, w, gen, n, t, args.steps))
+    os.write(json_fd, (json.dumps(res) + "\n").encode())
+
+
+def svd_extras(x, mean, w, gen, n, t, steps):
+    """`--workload svd --full`: the whole compute_svd call (first and steady), its eigen-solve, and the mode GEMM at three widths"""
+    from sparsespatialsampling_amd import svd
     t1 = time.perf_counter()
     s_, u_, v_ = svd.compute_svd(x, w, rank=50)
     pt.cuda.synchronize()
@@ -721,33 +748,20 @@ def bench_svd(args, json_fd):
     parts["eigh_library"] = ("rocSOLVER dsyevd behind s3_sym_eig (C ABI, dlopen)" if _s3lib.hip_lib().s3_sym_eig_available()
                              else "LAPACK on the host (torch.linalg.eigh): rocSOLVER not loadable")
     parts["eigh_share_of_compute_svd"] = parts["eigen_solve_ms"] * 1e-3 / float(np.median(steady))
-    achieved = flops / (st["kernel_ms"] * 1e-3) / 1e12
     # the tall GEMMs of the same SVD on the same matrix cores (s3_centered_gemm): the mode GEMM U = (X - mean) V S^-1 at the rank
     # compute_svd was asked for (50 columns occupy half of a 128-column tile) and at full width (the shape of a deflation level)
     gemm = {}
     for r in (50, 128, t):
         b = pt.empty((t, r), dtype=pt.float64, device="cuda").normal_(generator=gen)
-        gms = ms_stats(launch_times_ms(lambda: svd.centered_gemm(x, mean, b), max(3, args.steps // 4), 1))
+        gms = ms_stats(launch_times_ms(lambda: svd.centered_gemm(x, mean, b), max(3, steps // 4), 1))
         tf = 2.0 * n * t * r / (gms["kernel_ms"] * 1e-3) / 1e12
         gemm[f"r{r}"] = dict(columns=r, algorithmic_flops=2.0 * n * t * r, TFLOPs=tf, frac_of_sustained=tf / 46.0, frac_of_datasheet=tf / 78.6, **gms)
         del b
-    res = {"metric": "TFLOP/s weighted Gram matrix (f64 matrix cores)", "value": flops * args.steps / elapsed / 1e12, "unit": "TFLOP/s",
-           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": f"svd: weighted Gram matrix of {n} cells x {t} snapshots f64 (the bench grid's interpolated field)",
-                      "n_cells": n, "t_batch": t},
-           "device": device_identity(),
-           "roofline": {"bound": "mfma", "achieved": achieved, "peak": 78.6, "unit": "TFLOP/s", "frac": achieved / 78.6,
-                        "peak_source": "AMD MI355X datasheet, f64 matrix (the CDNA4 guide lists no f64 figure)",
-                        "sustained_instruction_rate": 46.0, "frac_of_sustained": achieved / 46.0,
-                        "sustained_source": "bare v_mfma_f64_16x16x4_f64 loop, operands in registers (tools/mfma_f64_peak.hip, HISTORY 5.6)",
-                        "kernel": "gram_block_kernel", "algorithmic_flops": flops, "traffic": None, **st},
-           "mode_gemm": dict(kernel="centered_gemm_kernel", shapes=gemm,
-                             note="C[N, r] = (X - mean 1^T) B, X [N, T] f64 as the interpolation left it, B [T, r]; flops 2 N T r"),
-           "eigh": "library", "compute_svd_s": svd_s, "compute_svd_steady_s": float(np.median(steady)), "compute_svd_parts": parts, "compute_svd_rank": int(len(s_)),
-           "compute_svd_note": "mean + Gram kernel + eigen-solve (rocSOLVER, the one library call) + mode GEMM (s3_centered_gemm), rank 50; "
-                               "compute_svd_s: first call of the process (the solver library initialises), compute_svd_steady_s: median of the next three"}
-    os.write(json_fd, (json.dumps(res) + "\n").encode())
+    return {"mode_gemm": dict(kernel="centered_gemm_kernel", shapes=gemm,
+                              note="C[N, r] = (X - mean 1^T) B, X [N, T] f64 as the interpolation left it, B [T, r]; flops 2 N T r"),
+            "eigh": "library", "compute_svd_s": svd_s, "compute_svd_steady_s": float(np.median(steady)), "compute_svd_parts": parts, "compute_svd_rank": int(len(s_)),
+            "compute_svd_note": "mean + Gram kernel + eigen-solve (rocSOLVER, the one library call) + mode GEMM (s3_centered_gemm), rank 50; "
+                                "compute_svd_s: first call of the process (the solver library initialises), compute_svd_steady_s: median of the next three"}
 
 
 # ---- N > 1 without a launcher: this process becomes the PARENT of N fresh ranks ---------------------------------------------
@@ -905,12 +919,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cylinder3D_Re3900", choices=sorted(WORKLOADS) + ["svd"])
     ap.add_argument("--t-batch", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baselines, the device-resident and the end-to-end legs (profiling runs)")
-    ap.add_argument("--no-batches", action="store_true", help="skip the roofline_batches sub-records")
-    ap.add_argument("--no-pitched-copy", action="store_true", help="skip the pitched_copy sub-record (profiling runs: its launches may "
+    ap.add_argument("--full", action="store_true", help="measure and check everything beside the headline as well: refine wall-clock, "
+                    "traffic, yardsticks, other batch shapes and layouts, transport legs, CPU baselines, grid digest, export leg (N > 1), "
+                    "compute_svd (--workload svd); the --no-* options below trim such a run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines, the device-resident and the end-to-end legs (profiling runs)")
+    ap.add_argument("--no-batches", action="store_true", help="--full: skip the roofline_batches sub-records")
+    ap.add_argument("--no-pitched-copy", action="store_true", help="--full: skip the pitched_copy sub-record (profiling runs: its launches may "
                     "carry the headline kernel's name -- 16-byte aligned rows of up to four chunks -- and would be averaged into its statistics)")
-    ap.add_argument("--no-traffic", action="store_true", help="do not measure roofline.traffic in this run (two rocprofv3 --pmc child passes "
-                    "before the GPU is touched); the recorded value of profiles/ is reported instead, labelled")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: do not measure roofline.traffic in this run (two rocprofv3 --pmc child "
+                    "passes before the GPU is touched); the recorded value of profiles/ is reported instead, labelled")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)      # (the short run a PMC pass profiles)
     ap.add_argument("--n-comp", type=int, default=1, help="components per snapshot: the row holds n_comp * t_batch values")
     ap.add_argument("--shard", choices=["cells", "snapshots"], default="cells",
@@ -929,9 +946,9 @@ def main():
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))            # no launcher around us: start (and watch) the N ranks ourselves
-    if args.traffic_child:                 # what a PMC pass profiles: the headline launch only, three times
+    if args.traffic_child:                 # what a PMC pass profiles: the headline launch three times, then the batch shapes
         args.steps, args.warmup = CHILD_LAUNCHES, 1
-        args.no_cpu_baseline = args.no_batches = args.no_pitched_copy = args.no_traffic = True
+        args.full = args.no_cpu_baseline = args.no_batches = args.no_pitched_copy = args.no_traffic = True
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -947,10 +964,10 @@ def main():
     os.dup2(2, 1)
 
     _mark("start")                         # (watchdog protocol of a self-launched run: nothing has touched the GPU yet)
-    if rank == 0:
+    if rank == 0 and args.full:
         query_rocm_smi()                   # (before anything initialises the GPU)
     measured = None
-    if rank == 0 and world == 1 and not args.no_traffic and args.workload != "svd" and not args.direct:
+    if rank == 0 and world == 1 and args.full and not args.no_traffic and args.workload != "svd" and not args.direct:
         # (also before anything initialises the GPU: the passes are child processes of this one)
         child_argv = [a for a in sys.argv[1:] if a not in ("--no-cpu-baseline", "--no-batches", "--no-pitched-copy")]
         child_argv = without_dump_outputs(child_argv)             # (the PMC passes write no outputs)
@@ -983,22 +1000,24 @@ def main():
     k = 26
     x, metric, geos, tree_kw = build_case(args.workload, cfg, geometry)
 
-    # ---- refine (grid generation), timed separately -----------------------------------------------------------
-    # one tiny run first: context creation, the load of the library's code objects and the first launch of every kernel
-    # are one-off start-up cost of the process, not of a grid generation
-    rng0 = np.random.default_rng(0)
-    xs = rng0.random((20000, 3))
-    warm = SamplingTree(pt.from_numpy(xs), pt.from_numpy(0.1 + np.exp(-4 * np.linalg.norm(xs - 0.5, axis=1))),
-                        [geometry.CubeGeometry("domain", True, [0.0, 0.0, 0.0], [1.0, 1.0, 1.0]),
-                         geometry.CylinderGeometry3D("c", False, [(0.5, 0.5, -1.0), (0.5, 0.5, 2.0)], 0.1, refine=True)],
-                        uniform_level=3, min_metric=0.3)
-    warm.refine()
-    warm.close()
-    del warm, xs
-    # the grid generation is timed four times: the first full-size run of the process also pays for the device allocations
-    # (cell arrays, topology tables, allocator pools) -- it is reported apart, `refine_wall_s` is the median of the other three
+    # ---- refine (grid generation), timed separately with --full -----------------------------------------------
+    if args.full:
+        # one tiny run first: context creation, the load of the library's code objects and the first launch of every kernel
+        # are one-off start-up cost of the process, not of a grid generation
+        rng0 = np.random.default_rng(0)
+        xs = rng0.random((20000, 3))
+        warm = SamplingTree(pt.from_numpy(xs), pt.from_numpy(0.1 + np.exp(-4 * np.linalg.norm(xs - 0.5, axis=1))),
+                            [geometry.CubeGeometry("domain", True, [0.0, 0.0, 0.0], [1.0, 1.0, 1.0]),
+                             geometry.CylinderGeometry3D("c", False, [(0.5, 0.5, -1.0), (0.5, 0.5, 2.0)], 0.1, refine=True)],
+                            uniform_level=3, min_metric=0.3)
+        warm.refine()
+        warm.close()
+        del warm, xs
+    # with --full the grid generation is timed four times: the first full-size run of the process also pays for the device
+    # allocations (cell arrays, topology tables, allocator pools) -- it is reported apart, `refine_wall_s` is the median of the
+    # other three.  A plain run generates the grid once.
     timings = []
-    for attempt in range(1 if args.traffic_child else 4):
+    for attempt in range(4 if args.full and not args.traffic_child else 1):
         pt.cuda.synchronize()
         comm.barrier()
         t0 = time.perf_counter()
@@ -1016,9 +1035,10 @@ def main():
         n_cells_total = tree._topo_engine.n_created
         tree.close()
         del tree
-    refine_first_s = timings[0][0]
-    refine_s = float(np.median([t[0] for t in timings[1:]]))            # median of three steady runs
-    t_init = float(np.median([t[1] for t in timings[1:]]))
+    if args.full:
+        refine_first_s = timings[0][0]
+        refine_s = float(np.median([t[0] for t in timings[1:]]))            # median of three steady runs
+        t_init = float(np.median([t[1] for t in timings[1:]]))
 
     # ---- KNN cache (once) -------------------------------------------------------------------------------------
     t0 = time.perf_counter()
@@ -1092,7 +1112,7 @@ def main():
     # the same launch on the pitched, compacted copy of the referenced rows (Hilbert order, whole 128-byte lines per row:
     # the layout ExportData uploads HOST batches into -- rounds 1-3 quoted the headline on it)
     pitched = None
-    if rank == 0 and world == 1 and plan is not None and not args.no_pitched_copy:
+    if rank == 0 and world == 1 and plan is not None and args.full and not args.no_pitched_copy:
         def pitched_leg():
             rows_p = hipops.gather_rows(data, used.contiguous(), hipops.padded_rows(n_rows, row_len, pt.float32, "cuda",
                                                                                    int(os.environ.get("S3_BENCH_PITCH_EXTRA", "0"))))
@@ -1106,7 +1126,7 @@ def main():
     # one process, 0.466 / 0.481 / 0.482 / 0.481 of peak in the same minute -- the boxes' "faster and slower states" are this): the
     # headline stays the allocation a caller gets, the same launch on a SECOND allocation of the same batch is recorded beside it
     placement = None
-    if rank == 0 and world == 1 and plan is not None and not args.no_pitched_copy and not args.traffic_child:
+    if rank == 0 and world == 1 and plan is not None and args.full and not args.no_pitched_copy and not args.traffic_child:
         def placement_leg():
             ref = out.clone()                         # the headline's result
             other = pt.empty_like(data)
@@ -1121,7 +1141,7 @@ def main():
 
     # N > 1: the product's export path with N ranks (every rank takes part; after the timed region of the headline)
     sharded_leg = None
-    if world > 1 and args.shard == "cells" and plan is not None and os.environ.get("S3_BENCH_NO_EXPORT_LEG") != "1":
+    if world > 1 and args.shard == "cells" and plan is not None and args.full and os.environ.get("S3_BENCH_NO_EXPORT_LEG") != "1":
         del data
         pt.cuda.empty_cache()
         # (the box workload in ITS batches: 16 snapshots per field and batch)
@@ -1144,9 +1164,9 @@ def main():
             pt.cuda.synchronize()
             del table, o, rows_p
         data = None
-    copy_bw = copy_bandwidth_gbs() if rank == 0 else None
+    copy_bw = copy_bandwidth_gbs() if rank == 0 and args.full else None
     yard = None
-    if rank == 0 and world == 1 and plan is not None and data is not None and not args.traffic_child and not args.no_pitched_copy:
+    if rank == 0 and world == 1 and plan is not None and data is not None and args.full and not args.traffic_child and not args.no_pitched_copy:
         yard = optional_leg("yardsticks", lambda: yardsticks(hipops, plan, data, args.steps, args.warmup))
     if rank == 0:
         units = (nc * world if args.shard == "snapshots" else nc_total) * t_b * args.steps
@@ -1159,38 +1179,38 @@ def main():
                     f"interpolate_data receives it, read in place ({n_rows} rows referenced) x {t_b} snapshots per step, "
                     f"{nc_total} generated cells, k={k}, fp32 in / f64 out")
         shape_key = f"T{t_b}" + (f"x{args.n_comp}" if args.n_comp > 1 else "")
-        traffic, traffic_src, traffic_stale = (recorded_traffic(f"{args.workload}/{shape_key}/inplace") if plan is not None and world == 1
-                                               else (None, None, None))
-        recorded = traffic
-        traffic_how = None if traffic is None else f"recorded, not measured in this run: {traffic_src}"
-        if measured is not None:           # measured in THIS run (two PMC child passes before the GPU was touched): preferred
-            traffic, traffic_how, traffic_stale = measured["traffic"], measured["how"], False
         res = {
             "metric": "Mcells*snapshots/s interpolated", "value": value, "unit": "Mcells*snapshots/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak" if args.shard == "snapshots" else "strong", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
+            "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": workload, "n_points": len(x), "resident_source_rows": n_rows, "n_cells": nc_total,
                        "t_batch": t_b, "k": k, "n_comp": args.n_comp, "shape_key": shape_key, "input": "dense device tensor, read in place",
                        "parallelism": f"{'snapshot-axis' if args.shard == 'snapshots' else 'leaf-cell'} shards x{world}",
                        "cells_per_rank": shard_counts, "collectives": comm.name},
             "device": device_identity(), "code_sha": code_sha(),
-            "refine_wall_s": refine_s, "refine_init_s": t_init, "refine_first_run_wall_s": refine_first_s,
-            "refine_runs_s": [t[0] for t in timings],
-            "refine_iterations": info["iterations"],
-            "refine_cells_created": n_cells_total, "refine_leaves_per_s": nc_total / refine_s, "knn_cache_s": knn_cache_s,
-            "captured_metric": info["metric_per_iter"][-1], "grid_sha256": sha_gpu,
+            "refine_iterations": info["iterations"], "refine_cells_created": n_cells_total, "knn_cache_s": knn_cache_s,
+            "captured_metric": info["metric_per_iter"][-1],
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
-                         "copy_kernel_GBs": copy_bw, "frac_of_copy_kernel": achieved / copy_bw,
-                         "traffic": traffic, "traffic_source": traffic_how, "traffic_stale": traffic_stale,
-                         "traffic_over_algorithmic": None if traffic is None else traffic / b_alg,
-                         "traffic_measured": measured, "traffic_recorded_in_profiles": recorded,
                          "kernel": "interp_kernel<float,4>" if plan is None else planned_kernel_name(row_len, k, plan.n_tiles, row_len, table_bytes=len(x) * row_len * 4),
                          "staged_rows_per_launch": None if plan is None else plan.total_rows, **ms_stats(launch_ms),
                          "frac_best_launch": b_alg / (min(launch_ms) * 1e-3) / 8e12,
                          "algorithmic_bytes": b_alg, "resident_source_rows": n_rows, "cells_on_this_rank": nc,
                          "gather_upper_bound_bytes": nc * k * row_len * 4 + nc * row_len * 8},
         }
+        if args.full:
+            traffic, traffic_src, traffic_stale = (recorded_traffic(f"{args.workload}/{shape_key}/inplace") if plan is not None and world == 1
+                                                   else (None, None, None))
+            recorded = traffic
+            traffic_how = None if traffic is None else f"recorded, not measured in this run: {traffic_src}"
+            if measured is not None:           # measured in THIS run (two PMC child passes before the GPU was touched): preferred
+                traffic, traffic_how, traffic_stale = measured["traffic"], measured["how"], False
+            res.update({"refine_wall_s": refine_s, "refine_init_s": t_init, "refine_first_run_wall_s": refine_first_s,
+                        "refine_runs_s": [t[0] for t in timings], "refine_leaves_per_s": nc_total / refine_s, "grid_sha256": sha_gpu})
+            res["roofline"].update({"copy_kernel_GBs": copy_bw, "frac_of_copy_kernel": achieved / copy_bw,
+                                    "traffic": traffic, "traffic_source": traffic_how, "traffic_stale": traffic_stale,
+                                    "traffic_over_algorithmic": None if traffic is None else traffic / b_alg,
+                                    "traffic_measured": measured, "traffic_recorded_in_profiles": recorded})
         if yard is not None:
             res["roofline"]["yardsticks"] = yard
             mix = yard.get("mix_7r2w", {}).get("GBs", 0.0)
@@ -1215,7 +1235,7 @@ def main():
             res["roofline"]["pitched_copy"] = pitched
         if sharded_leg is not None:
             res["export_sharded"] = sharded_leg
-        if world == 1 and plan is not None and not args.no_batches:
+        if world == 1 and plan is not None and args.full and not args.no_batches:
             # the batch lengths the reference exports with (examples/s3_for_cylinder3D_Re3900.py:28-69, utils.py:204-226)
             key = args.workload
             res["roofline_batches"] = {name: optional_leg(f"roofline_batches.{name}", lambda rl=rl, label=label, name=name: batch_record(
@@ -1225,7 +1245,7 @@ def main():
             if "kernel_ms" in res["roofline_batches"].get("T25", {}):
                 res["roofline_batches"]["T25"]["numbering_follows_space"] = optional_leg("numbering_follows_space", lambda: numbering_follows_space(
                     hipops, x, idx, used, w, my_centers, k, 25, args.steps, args.warmup, gen))
-        if not args.no_cpu_baseline and world == 1:       # reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:       # reported at N=1 only
             bare = {t_b: kernel_ms}
             if "kernel_ms" in res.get("roofline_batches", {}).get("T25", {}):
                 bare[25] = res["roofline_batches"]["T25"]["kernel_ms"]

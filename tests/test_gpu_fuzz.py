@@ -25,11 +25,11 @@ def test_fuzz_tool(tool, seed, cases):
 
 @pytest.mark.gpu
 def test_bench_contract_small_workload():
-    """bench.py on the reduced workload: exactly one line on stdout, valid JSON, the keys of the driver's contract plus the
+    """bench.py --full on the reduced workload: exactly one line on stdout, valid JSON, the keys of the driver's contract plus the
     roofline and cpu_baseline objects"""
     import json
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cylinder3D_small", "--steps", "3",
-                          "--warmup", "1"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--warmup", "1", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = run.stdout.strip().splitlines()
     assert len(lines) == 1, run.stdout[-2000:]
@@ -68,6 +68,42 @@ def test_bench_contract_small_workload():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean(tmp_path):
+    """bench.py without --full does what its headline needs and nothing beside it: one JSON line with the driver's contract and
+    the roofline of the timed launches, none of the legs of --full -- and the outputs of its last timed step are, bit for bit,
+    those of a --full run (which generates the grid five times instead of once)"""
+    import json
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cylinder3D_small", "--steps", "3", "--warmup", "1"]
+    plain = subprocess.run(base + ["--dump-outputs", str(tmp_path / "plain")], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert plain.returncode == 0, plain.stderr[-2000:]
+    lines = plain.stdout.strip().splitlines()
+    assert len(lines) == 1, plain.stdout[-2000:]
+    res = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert key in res, key
+    assert res["full"] is False and res["steps"] == 3 and res["warmup"] == 1 and res["value"] > 0 and res["dtype"] == "f64"
+    assert res["unit"] == "Mcells*snapshots/s" and res["higher_is_better"] is True and res["ms_per_step"] > 0
+    for key in ("refine_wall_s", "refine_runs_s", "grid_sha256", "roofline_batches", "device_resident_input", "end_to_end",
+                "cpu_baseline", "refine_cpu_baseline", "gpu_over_cpu"):
+        assert key not in res, key
+    for key in ("traffic", "traffic_measured", "copy_kernel_GBs", "yardsticks", "pitched_copy", "second_allocation"):
+        assert key not in res["roofline"], key
+    assert res["roofline"]["launches"] == 3 and 0 < res["roofline"]["frac"] < 1
+    full = subprocess.run(base + ["--full", "--no-cpu-baseline", "--no-batches", "--no-traffic", "--dump-outputs", str(tmp_path / "full")],
+                          cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert full.returncode == 0, full.stderr[-2000:]
+    rf = json.loads(full.stdout.strip().splitlines()[-1])
+    assert rf["full"] is True and "refine_wall_s" in rf and "pitched_copy" in rf["roofline"]
+    assert rf["config"] == res["config"] and rf["captured_metric"] == res["captured_metric"]
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) == ["cell_centers.npy", "cell_ids.npy", "interpolated.npy"]
+    for name in names:
+        a, b = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
+        assert a.dtype == b.dtype and np.array_equal(a, b), name
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_share_one_gpu():
     """rehearsal of the N = 2 path on one GPU (two processes, gloo for the exchange steps): the grid and the captured
     metric must be the ones of the single-rank run (rank-count independent reduction), the bench line says leaf-cell
@@ -93,7 +129,7 @@ def _self_launched_bench(extra_env, timeout=900, gpus=2):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "S3_DIST_BACKEND"):
         env.pop(k, None)
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--workload", "cylinder3D_small", "--steps", "2",
-                          "--warmup", "1", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
+                          "--warmup", "1", "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     return run, [json.loads(ln) for ln in run.stdout.splitlines() if ln.startswith("{")]
 
 
@@ -113,7 +149,7 @@ def test_bench_five_ranks_share_one_gpu():
     assert line["export_sharded"]["data_path_collectives_per_batch"] == 0 and "ms_per_batch" in line["export_sharded"]
     import json
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cylinder3D_small", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     r1 = json.loads(one.stdout.strip().splitlines()[-1])
     assert r1["config"]["n_cells"] == line["config"]["n_cells"] and r1["captured_metric"] == line["captured_metric"]
@@ -160,7 +196,7 @@ def test_bench_line_survives_a_failing_leg():
     import json
     env = dict(os.environ, S3_BENCH_FAIL_LEG="roofline_batches.T25")
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cylinder3D_small", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-2000:]
     line = json.loads(run.stdout.strip().splitlines()[-1])
     assert line["value"] > 0 and 0 < line["roofline"]["frac"] < 1 and "kernel_ms" in line["roofline"]["pitched_copy"]

@@ -12,7 +12,7 @@ cd /tmp
 echo "Kernel_Name,Counter_Name,Counter_Value" > "$out/pmc_extra.csv"
 for group in "TCC_HIT_sum TCC_MISS_sum" "TCC_REQ_sum TCC_READ_sum" "TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum" "SQ_WAVE_CYCLES SQ_WAIT_ANY" "SQ_BUSY_CYCLES SQ_WAVES" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "SQ_INSTS_LDS SQ_INSTS_VALU"; do
     gname=$(echo $group | tr ' ' '_')
-    if rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$out/x_$gname" -- python "$root/bench.py" --steps 3 --warmup 1 --no-cpu-baseline "$@" > "$out/x_$gname.log" 2>&1; then
+    if rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$out/x_$gname" -- python "$root/bench.py" --steps 3 --warmup 1 --full --no-cpu-baseline "$@" > "$out/x_$gname.log" 2>&1; then
         f=$(find "$out/x_$gname" -name "*counter_collection.csv" | head -n 1)
         python - "$f" "$out/pmc_extra.csv" <<'PY'
 import csv, sys

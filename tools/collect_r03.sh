@@ -10,12 +10,12 @@ S3_BENCH_FAST=1 bash tools/collect_profile.sh r03 cylinder3D_T100 --t-batch 100 
 if [ "$lease" = "1" ]; then
     S3_BENCH_FAST=1 bash tools/collect_profile.sh r03 box5e7 --workload box5e7 || exit 1
     root=$(pwd); out=$root/gpurun_out/prof_r03/extra; mkdir -p $out; export TMPDIR=/tmp
-    python bench.py --workload svd > $out/bench_svd.json 2> $out/bench_svd.err
+    python bench.py --workload svd --full > $out/bench_svd.json 2> $out/bench_svd.err
     cd /tmp
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out/svd -- python $root/bench.py --workload svd --steps 5 --warmup 2 > $out/svd.log 2>&1
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out/svd -- python $root/bench.py --workload svd --steps 5 --warmup 2 --full > $out/svd.log 2>&1
     find $out/svd -name "*kernel_stats.csv" -exec cp {} $out/svd_kernel_stats.csv \; ; rm -rf $out/svd
     for w in cylinder3D_Re3900 box5e7; do
-        rocprofv3 --kernel-trace --stats --output-format csv -d $out/refine_$w -- python $root/bench.py --workload $w --no-cpu-baseline --no-batches --steps 2 --warmup 1 > $out/refine_$w.log 2>&1
+        rocprofv3 --kernel-trace --stats --output-format csv -d $out/refine_$w -- python $root/bench.py --workload $w --full --no-cpu-baseline --no-batches --steps 2 --warmup 1 > $out/refine_$w.log 2>&1
         find $out/refine_$w -name "*kernel_stats.csv" -exec cp {} $out/refine_${w}_kernel_stats.csv \; ; rm -rf $out/refine_$w
     done
     cd $root

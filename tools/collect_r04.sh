@@ -11,13 +11,13 @@ S3_BENCH_FAST=1 bash tools/collect_profile.sh r04 cylinder3D_T100 --t-batch 100 
 if [ "$lease" = "1" ]; then
     S3_BENCH_FAST=1 bash tools/collect_profile.sh r04 box5e7 --workload box5e7 || exit 1
     root=$(pwd); out=$root/gpurun_out/prof_r04/extra; mkdir -p $out; export TMPDIR=/tmp
-    python bench.py --workload svd > $out/bench_svd.json 2> $out/bench_svd.err
+    python bench.py --workload svd --full > $out/bench_svd.json 2> $out/bench_svd.err
     cd /tmp
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out/svd -- python $root/bench.py --workload svd --steps 5 --warmup 2 > $out/svd.log 2>&1
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out/svd -- python $root/bench.py --workload svd --steps 5 --warmup 2 --full > $out/svd.log 2>&1
     find $out/svd -name "*kernel_stats.csv" -exec cp {} $out/svd_kernel_stats.csv \; ; rm -rf $out/svd
     cd $root
     S3_BENCH_SHARE_GPU=1 S3_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29655 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_2ranks_one_gpu.json 2> $out/bench_2ranks_one_gpu.err
+        --master-port 29655 bench.py --gpus 2 --steps 5 --warmup 2 --full --no-cpu-baseline > $out/bench_2ranks_one_gpu.json 2> $out/bench_2ranks_one_gpu.err
     python tools/e2e_probe.py 200 > $out/e2e_probe_T200.txt 2>&1
     python tools/e2e_probe.py 25 12 > $out/e2e_probe_T25.txt 2>&1
     python tools/transport_probe.py 1.0 > $out/transport_probe.txt 2>&1

@@ -17,8 +17,8 @@ if [ "$part" = "all" ] || [ "$part" = "shapes" ]; then
 fi
 if [ "$part" = "all" ] || [ "$part" = "extra" ]; then
     root=$(pwd); out=$root/gpurun_out/prof_r06/extra; mkdir -p $out; export TMPDIR=/tmp
-    python bench.py --workload svd > $out/bench_svd.json 2> $out/bench_svd.err
-    S3_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_2ranks_self_launched.json 2> $out/bench_2ranks_self_launched.err
-    S3_BENCH_SHARE_GPU=1 python bench.py --gpus 5 --workload cylinder3D_small --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_5ranks_small.json 2> $out/bench_5ranks_small.err
+    python bench.py --workload svd --full > $out/bench_svd.json 2> $out/bench_svd.err
+    S3_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 5 --warmup 2 --full --no-cpu-baseline > $out/bench_2ranks_self_launched.json 2> $out/bench_2ranks_self_launched.err
+    S3_BENCH_SHARE_GPU=1 python bench.py --gpus 5 --workload cylinder3D_small --steps 5 --warmup 2 --full --no-cpu-baseline > $out/bench_5ranks_small.json 2> $out/bench_5ranks_small.err
     python examples/s3_for_synthetic_OAT15.py /tmp/s3_oat15 500 > $out/example_oat15.txt 2>&1; ls -la /tmp/s3_oat15 >> $out/example_oat15.txt 2>&1; rm -rf /tmp/s3_oat15
 fi

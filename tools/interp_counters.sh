@@ -9,7 +9,7 @@ csv="$root/gpurun_out/interp_counters_$name.csv"
 echo "Kernel_Name,Counter_Name,mean_per_launch,launches" > "$csv"
 for group in "SQ_WAVE_CYCLES SQ_WAIT_ANY" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU" "SQ_INSTS_VALU SQ_INSTS_LDS" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" "SQ_INSTS_SALU SQ_INSTS_SMEM" "SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS" "SQ_BUSY_CYCLES SQ_WAVES" "SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR"; do
     gname=$(echo $group | tr ' ' '_')
-    if rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$out/x_$gname" -- python "$root/bench.py" --steps 3 --warmup 1 --no-cpu-baseline "$@" > "$out/x_$gname.log" 2>&1; then
+    if rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$out/x_$gname" -- python "$root/bench.py" --steps 3 --warmup 1 --full --no-cpu-baseline "$@" > "$out/x_$gname.log" 2>&1; then
         f=$(find "$out/x_$gname" -name "*counter_collection.csv" | head -n 1)
         python - "$f" "$csv" <<'PY'
 import csv, sys

@@ -4,7 +4,7 @@
 set -o pipefail
 w=${1:-cylinder3D_Re3900}
 root=$(pwd); out=$root/gpurun_out; mkdir -p "$out"; export TMPDIR=/tmp; cd /tmp
-rocprofv3 --kernel-trace --output-format csv -d "$out/kb_$w" -- python3 "$root/bench.py" --workload "$w" --no-cpu-baseline --no-batches --steps 2 --warmup 1 > "$out/kb_$w.log" 2>&1 || exit 1
+rocprofv3 --kernel-trace --output-format csv -d "$out/kb_$w" -- python3 "$root/bench.py" --workload "$w" --full --no-cpu-baseline --no-batches --steps 2 --warmup 1 > "$out/kb_$w.log" 2>&1 || exit 1
 f=$(find "$out/kb_$w" -name "*kernel_trace.csv" | head -n 1)
 python3 - "$f" > "$out/knn_batches_$w.txt" <<'PY'
 import csv, sys, re

@@ -4,7 +4,7 @@
 set -o pipefail
 w=${1:-cylinder3D_Re3900}
 root=$(pwd); out=$root/gpurun_out; mkdir -p "$out"; export TMPDIR=/tmp; cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/rks_$w" -- python3 "$root/bench.py" --workload "$w" --no-cpu-baseline --no-batches --steps 2 --warmup 1 > "$out/rks_$w.log" 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/rks_$w" -- python3 "$root/bench.py" --workload "$w" --full --no-cpu-baseline --no-batches --steps 2 --warmup 1 > "$out/rks_$w.log" 2>&1 || exit 1
 find "$out/rks_$w" -name "*kernel_stats.csv" -exec cp {} "$out/refine_${w}_kernel_stats.csv" \; ; rm -rf "$out/rks_$w"
 python3 - "$out/refine_${w}_kernel_stats.csv" <<'PY'
 import csv, sys, re
