@@ -19,6 +19,7 @@ _MODULES = {
     "geometry": "geometry", "geometry.geometry_base": "geometry.geometry_base",
     "geometry.cube_geometry": "geometry.cube_geometry", "geometry.sphere_geometry": "geometry.sphere_geometry",
     "geometry.cylinder_geometry": "geometry.cylinder_geometry", "geometry.coordinates_2d": "geometry.coordinates_2d",
+    "geometry.geometry_STL_3d": "geometry.geometry_STL_3d",
     # the four polytope bodies live in one module here
     "geometry.triangle_geometry": "geometry.polytope_geometry", "geometry.prism_geometry": "geometry.polytope_geometry",
     "geometry.tetrahedron_geometry": "geometry.polytope_geometry", "geometry.pyramid_geometry": "geometry.polytope_geometry",

@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 7
+#define S3_ABI_VERSION 8
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -160,7 +160,10 @@ int s3_child_gain_reuse(const s3_knn *knn, int k, const double *d_center, const 
  *   prism:    0 <= proj <= norm && in-plane point inside triangle    prism_geometry.py:90-118
  *   tetrahedra (1 = tetrahedron, 2 = the two halves of a pyramid, union): no inward face normal sees the point
  *             behind its face                                        tetrahedron_geometry.py:121-140,
- *                                                                    pyramid_geometry.py:156-170 */
+ *                                                                    pyramid_geometry.py:156-170
+ *   mesh (closed triangle surface, 3-D): on the surface, or the +x ray crosses it an odd number of times -- the package's own
+ *             exact rule (geometry/geometry_STL_3d.py states it per facet); stands in for vtkSelectEnclosedPoints of
+ *                                                                    geometry_STL_3d.py:86-104 */
 int s3_mask_box(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n, int dim,
                 double width, const double *h_lo, const double *h_hi, int refine_mode, int keep_inside,
                 uint8_t *d_invalid, s3_stream stream);
@@ -185,6 +188,16 @@ int s3_mask_tetrahedra(const double *d_center, const int32_t *d_level, const int
                        double width, const double *h_positions /*[n_tets][4][3]*/,
                        const double *h_normals /*[n_tets][3][4] inward, column p belongs to point p*/, int n_tets,
                        int refine_mode, int keep_inside, uint8_t *d_invalid, s3_stream stream);
+
+/* d_tri: facets with their vertices in lexicographic (x, y, z) order; h_lo / h_hi: bounding box of the surface (a node outside
+ * it is outside before any table is read); d_bin_start / d_bin_facet: CSR lists of a uniform ny x nz grid of (y, z) columns over
+ * that box, column (iy, iz) at iy*nz + iz with i = clamp(floor((v - lo) * (n / (hi - lo))), 0, n - 1) (scale 0 for a flat extent),
+ * each listing every facet whose closed projected bounding box touches the column (ny = nz = 1: all facets, brute force).  One
+ * lane per (cell, node); facet ids must be < nt and bin_start[ny*nz] the length of d_bin_facet (not checked on the device). */
+int s3_mask_mesh(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
+                 double width, const double *d_tri /*[nt][3][3]*/, int nt, const double *h_lo /*[3]*/,
+                 const double *h_hi /*[3]*/, const int32_t *d_bin_start /*[ny*nz+1]*/, const int32_t *d_bin_facet, int ny,
+                 int nz, int refine_mode, int keep_inside, uint8_t *d_invalid, s3_stream stream);
 
 /* bookkeeping of one refine batch on the device-resident cell arrays: parents stop being leaves, valid children
  * become leaves, invalid children get gain 0 (s_cube.py:721-723, 250-251) */

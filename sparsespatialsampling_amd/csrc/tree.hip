@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -184,6 +185,94 @@ static int check_mask_args(const void *center, const void *level, int64_t first,
     S3_REQUIRE(n >= 0 && first >= 0, "%s: bad range", who);
     S3_REQUIRE(n == 0 || (center && level && inv), "%s: null array", who);
     return S3_OK;
+}
+
+// closed triangle mesh: on the surface, or an odd number of facets crossed by the ray in +x.  The rule per facet, its operations
+// and their order are those of inside_mesh() in geometry/geometry_STL_3d.py -- the two must agree bit for bit.
+struct MeshParams {
+    const double *tri;           // [nt][3][3], vertices of a facet in lexicographic order
+    const int32_t *bin_start;    // [ny*nz+1]
+    const int32_t *bin_facet;
+    int ny, nz;
+    double lo[3], hi[3], sy, sz;
+};
+
+__device__ __forceinline__ int mesh_column(double v, double lo, double scale, int nb) {
+    const double b = floor((v - lo) * scale);           // v lies in the bounding box: 0 <= b <= nb up to rounding
+    return b < 1.0 ? 0 : (b >= (double)nb ? nb - 1 : (int)b);
+}
+
+__device__ __forceinline__ bool mesh_edge_hit(double py, double pz, double p_y, double p_z, double q_y, double q_z) {
+    if ((p_z > pz) == (q_z > pz)) return false;
+    return py < p_y + (pz - p_z) * (q_y - p_y) / (q_z - p_z);
+}
+
+__device__ __forceinline__ bool mesh_closed_triangle(double pu, double pv, double au, double av, double bu, double bv,
+                                                     double cu, double cv) {
+    const double s0 = (bu - au) * (pv - av) - (bv - av) * (pu - au);
+    const double s1 = (cu - bu) * (pv - bv) - (cv - bv) * (pu - bu);
+    const double s2 = (au - cu) * (pv - cv) - (av - cv) * (pu - cu);
+    return !(((s0 < 0) | (s1 < 0) | (s2 < 0)) & ((s0 > 0) | (s1 > 0) | (s2 > 0)));
+}
+
+// 2: the point lies on the facet, 1: its ray in +x crosses the facet, 0: neither
+__device__ __forceinline__ int mesh_facet(const double *__restrict__ t, double px, double py, double pz) {
+    const double ay = t[1], az = t[2], by = t[4], bz = t[5], cy = t[7], cz = t[8];
+    if (!((py >= fmin(fmin(ay, by), cy)) & (py <= fmax(fmax(ay, by), cy)) & (pz >= fmin(fmin(az, bz), cz)) &
+          (pz <= fmax(fmax(az, bz), cz))))
+        return 0;
+    const double ax = t[0], bx = t[3], cx = t[6];
+    const double e1x = bx - ax, e1y = by - ay, e1z = bz - az, e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
+    const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    const double vol = (nx * (px - ax) + ny * (py - ay)) + nz * (pz - az);
+    if (vol == 0.0) {
+        const double fx = fabs(nx), fy = fabs(ny), fz = fabs(nz);
+        bool on;
+        if ((fx >= fy) & (fx >= fz)) on = mesh_closed_triangle(py, pz, ay, az, by, bz, cy, cz);
+        else if (fy >= fz) on = mesh_closed_triangle(pz, px, az, ax, bz, bx, cz, cx);
+        else on = mesh_closed_triangle(px, py, ax, ay, bx, by, cx, cy);
+        return on ? 2 : 0;
+    }
+    if ((nx == 0.0) | ((vol < 0.0) == (nx < 0.0))) return 0;       // parallel to the ray, or met at x <= px
+    return (int)(mesh_edge_hit(py, pz, ay, az, by, bz) ^ mesh_edge_hit(py, pz, ay, az, cy, cz) ^
+                 mesh_edge_hit(py, pz, by, bz, cy, cz));
+}
+
+// one lane per (cell, node): 32 cells per workgroup, the 8 lanes of a cell are adjacent in one wavefront.  The facet walks have
+// different lengths per lane, so nothing synchronises inside them; the verdicts meet in one ballot after the walk.
+__global__ void __launch_bounds__(256)
+mask_mesh_kernel(const double *__restrict__ center, const int32_t *__restrict__ level, const int32_t *__restrict__ cells,
+                 int64_t first, int64_t n, double half_width, MeshParams g, int refine_mode, int keep_inside,
+                 uint8_t *__restrict__ invalid) {
+    const int64_t t = blockIdx.x * (int64_t)256 + threadIdx.x;
+    const int64_t i = t >> 3;
+    const int c = (int)(t & 7);
+    bool in = false;
+    if (i < n) {
+        const int64_t cell = cells ? (int64_t)cells[i] : first + i;
+        const double off = cell_offset(half_width, level[cell]);
+        const double px = center[cell * 3 + 0] + dir_comp(3, c, 0) * off;
+        const double py = center[cell * 3 + 1] + dir_comp(3, c, 1) * off;
+        const double pz = center[cell * 3 + 2] + dir_comp(3, c, 2) * off;
+        if ((px >= g.lo[0]) & (px <= g.hi[0]) & (py >= g.lo[1]) & (py <= g.hi[1]) & (pz >= g.lo[2]) & (pz <= g.hi[2])) {
+            const int b = mesh_column(py, g.lo[1], g.sy, g.ny) * g.nz + mesh_column(pz, g.lo[2], g.sz, g.nz);
+            int odd = 0;
+            for (int k = g.bin_start[b], e = g.bin_start[b + 1]; k < e; ++k) {
+                const int r = mesh_facet(g.tri + 9 * (int64_t)g.bin_facet[k], px, py, pz);
+                if (r == 2) {
+                    odd = 1;
+                    break;
+                }
+                odd ^= r;
+            }
+            in = odd != 0;
+        }
+    }
+    const unsigned long long votes = __ballot(in);
+    if (c == 0 && i < n) {
+        const int n_in = __popc((unsigned)((votes >> (threadIdx.x & 56)) & 0xffull));
+        invalid[i] |= combine(n_in, 8, refine_mode, keep_inside);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -605,6 +694,36 @@ int s3_mask_tetrahedra(const double *d_center, const int32_t *d_level, const int
     mask_kernel<3, TetParams><<<grid_for(n, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_cells, first, n,
                                                                               0.5 * width, g, refine_mode, keep_inside,
                                                                               d_invalid);
+    S3_LAUNCH_CHECK();
+    return S3_OK;
+}
+
+int s3_mask_mesh(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
+                 double width, const double *d_tri, int nt, const double *h_lo, const double *h_hi,
+                 const int32_t *d_bin_start, const int32_t *d_bin_facet, int ny, int nz, int refine_mode, int keep_inside,
+                 uint8_t *d_invalid, s3_stream stream) {
+    if (int rc = check_mask_args(d_center, d_level, first, n, 3, d_invalid, "s3_mask_mesh")) return rc;
+    S3_REQUIRE(d_tri && nt >= 1 && h_lo && h_hi, "s3_mask_mesh: no facets or no bounding box");
+    S3_REQUIRE(d_bin_start && d_bin_facet && ny >= 1 && nz >= 1 && (int64_t)ny * nz < ((int64_t)1 << 31),
+               "s3_mask_mesh: bad column table");
+    S3_REQUIRE(n < ((int64_t)1 << 31), "s3_mask_mesh: too many cells");
+    if (n == 0) return S3_OK;
+    MeshParams g{};
+    g.tri = d_tri;
+    g.bin_start = d_bin_start;
+    g.bin_facet = d_bin_facet;
+    g.ny = ny;
+    g.nz = nz;
+    for (int j = 0; j < 3; ++j) {
+        g.lo[j] = h_lo[j];
+        g.hi[j] = h_hi[j];
+    }
+    g.sy = (double)ny / (h_hi[1] - h_lo[1]);
+    g.sz = (double)nz / (h_hi[2] - h_lo[2]);
+    if (!std::isfinite(g.sy)) g.sy = 0.0;          // flat extent: one column
+    if (!std::isfinite(g.sz)) g.sz = 0.0;
+    mask_mesh_kernel<<<grid_for(n * 8, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_cells, first, n, 0.5 * width,
+                                                                         g, refine_mode, keep_inside, d_invalid);
     S3_LAUNCH_CHECK();
     return S3_OK;
 }

@@ -65,7 +65,8 @@ class GeometryObject(ABC):
     def kernel_spec(self):
         """``(kind, params...)`` consumed by the device mask kernels: ``("box", lo, hi)``, ``("sphere", pos, r)``,
         ``("cylinder", p0, axis, norm, r0, r1, is_cone)``, ``("polygon", xy[nv,2])``, ``("triangle", xy[3,2])``,
-        ``("prism", origin, axis, norm, dims, xy[3,2])`` or ``("tetrahedra", pos[n,4,3], normals[n,3,4])``.
+        ``("prism", origin, axis, norm, dims, xy[3,2])``, ``("tetrahedra", pos[n,4,3], normals[n,3,4])`` or
+        ``("mesh", tri[nt,3,3], lo, hi, ny, nz, bin_start, bin_facet)``.
 
         ``None`` (the default): this geometry has no device predicate.  The refine loop then downloads the node coordinates
         of the cells in question and asks ``check_cell`` cell by cell -- any user-defined geometry with the reference's

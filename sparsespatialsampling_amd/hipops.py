@@ -635,6 +635,38 @@ def mask_tetrahedra(center, level, cells, first, n, width, positions, normals, r
           "s3_mask_tetrahedra")
 
 
+class MeshTable:
+    """device image of a closed triangle mesh for ``mask_mesh``: facets ``tri [nt, 3, 3]`` (vertices of a facet in
+    lexicographic order), bounding box ``lo`` / ``hi`` and the CSR column table ``(ny, nz, bin_start, bin_facet)`` of
+    ``geometry.geometry_STL_3d.build_column_bins`` -- uploaded once; the table is checked here, the kernel trusts it"""
+
+    def __init__(self, tri, lo, hi, ny, nz, bin_start, bin_facet):
+        tri = np.ascontiguousarray(tri, dtype=np.float64)
+        bin_start = np.ascontiguousarray(bin_start, dtype=np.int32)
+        bin_facet = np.ascontiguousarray(bin_facet, dtype=np.int32)
+        self.nt, self.ny, self.nz = int(tri.shape[0]), int(ny), int(nz)
+        if tri.shape != (self.nt, 3, 3) or self.nt < 1:
+            raise ValueError("MeshTable: facets [nt, 3, 3] expected")
+        if (self.ny < 1 or self.nz < 1 or bin_start.shape != (self.ny * self.nz + 1,) or bin_start[0] != 0
+                or (np.diff(bin_start) < 0).any() or bin_start[-1] != len(bin_facet)
+                or (len(bin_facet) and (bin_facet.min() < 0 or bin_facet.max() >= self.nt))):
+            raise ValueError("MeshTable: inconsistent column table")
+        self.lo, self.hi = _host_f64(lo), _host_f64(hi)
+        self.tri = to_device(tri)
+        self.bin_start = to_device(bin_start)
+        self.bin_facet = to_device(bin_facet if len(bin_facet) else np.zeros(1, dtype=np.int32))
+
+
+def mask_mesh(center, level, cells, first, n, width, mesh, refine_mode, keep_inside, invalid):
+    if int(center.shape[1]) != 3:
+        raise ValueError("mask_mesh: a triangle mesh is a 3-D body")
+    check(_lib.hip_lib().s3_mask_mesh(_ptr(center), _ptr(level), _ptr(cells), int(first), int(n), float(width),
+                                      _ptr(mesh.tri), mesh.nt, mesh.lo.ctypes.data_as(C.c_void_p),
+                                      mesh.hi.ctypes.data_as(C.c_void_p), _ptr(mesh.bin_start), _ptr(mesh.bin_facet),
+                                      mesh.ny, mesh.nz, int(refine_mode), int(keep_inside), _ptr(invalid), _stream()),
+          "s3_mask_mesh")
+
+
 def commit_batch(leaf, gain, parents, first, n_new, invalid):
     n_par = int(parents.numel()) if parents is not None else 0
     check(_lib.hip_lib().s3_commit_batch(_ptr(leaf), _ptr(gain), _ptr(parents), n_par, int(first), int(n_new),

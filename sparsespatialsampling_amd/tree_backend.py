@@ -160,6 +160,12 @@ class HipTreeBackend:
             elif spec[0] == "tetrahedra":
                 hipops.mask_tetrahedra(self.center, self.level, d_cells, first, n, w, spec[1], spec[2], refine_mode, ki,
                                        invalid)
+            elif spec[0] == "mesh":
+                key = id(g)
+                if key not in self._poly_cache:
+                    self._poly_cache[key] = hipops.MeshTable(*spec[1:])
+                hipops.mask_mesh(self.center, self.level, d_cells, first, n, w, self._poly_cache[key], refine_mode, ki,
+                                 invalid)
             else:
                 raise NotImplementedError(f"geometry kind {spec[0]!r} has no device kernel")
         self._last_invalid = invalid
