@@ -8,6 +8,7 @@
 #include <cstdio>
 
 #include "s3hip.h"
+#include "topo_core.h"
 
 namespace s3 {
 
@@ -41,13 +42,8 @@ inline unsigned grid_for(int64_t n, int block, int64_t cap = (int64_t)1 << 30) {
     return (unsigned)g;
 }
 
-// child / node direction table of the reference (s_cube.py:188-194); component j of direction c
-__device__ __forceinline__ double dir_comp(int /*dim*/, int c, int j) {
-    // 2-D: (-1,-1) (-1,1) (1,1) (1,-1); 3-D: the same four with z=+1, then with z=-1
-    if (j == 0) return (c & 3) >= 2 ? 1.0 : -1.0;
-    if (j == 1) return ((c & 3) == 1 || (c & 3) == 2) ? 1.0 : -1.0;
-    return c < 4 ? 1.0 : -1.0;
-}
+// child / node direction table of the reference: the one of the topology core (csrc/topo_core.h)
+__device__ __forceinline__ double dir_comp(int /*dim*/, int c, int j) { return s3topo::dir_comp(c, j); }
 
 // (factor*width)/2^level exactly as torch evaluates it at s_cube.py:441 (all operations are exact scalings)
 __device__ __forceinline__ double cell_offset(double factor_width, int level) {

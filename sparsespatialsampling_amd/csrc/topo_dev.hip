@@ -3,7 +3,7 @@
 //
 // Reference behaviour restated here (file:line relative to the reference checkout):
 //   Cell                         s_cube.py:32-83      -> structure-of-arrays (level, parent, first_child, nb, node_idx)
-//   _assign_neighbors            s_cube.py:904-1186   -> lattice rule table (built on the host as in topology.cpp)
+//   _assign_neighbors            s_cube.py:904-1186   -> lattice rule table (topo_core.h, built on the host)
 //   _assign_indices              s_cube.py:1188-1536  -> topo_tables.h decision tables
 //   check_nb_node                s_cube.py:1739-1755
 //   _remove_invalid_cells (nb)   s_cube.py:721-728
@@ -15,7 +15,8 @@
 //   * refine: children ids are known up front (first + 2^d * position), so every parent evaluates "was my neighbour
 //     refined before me" from the state before the batch plus its position (pass A: links and node entries, new nodes
 //     counted per parent; scan; pass C: ids + coordinates of the new nodes; pass D: references into earlier parents'
-//     children are followed to a final id) -- the four-pass form of csrc/topology.cpp;
+//     children are followed to a final id) -- the per-parent core of csrc/topo_core.h, the same source the batch form of
+//     the host engine (csrc/topology.cpp) runs on its thread pool;
 //   * relink (cell.parent.children = _assign_neighbors(...), s_cube.py:609, 834): a refresh of parent p rewrites the rows
 //     of p's children from p's own row, so the result of the ordered list depends only on, per listed parent, the time
 //     of its last refresh and the last refresh of each ancestor before that: every listed parent walks up that chain,
@@ -24,14 +25,13 @@
 //   * mark invalid: x removes itself from the rows of the neighbours listed in its own row *as that row is when x's turn
 //     comes*; an entry y of x's row has been wiped by then exactly if y comes earlier in the list and had x in its row,
 //     which is decided from the rows before the call (pass 1), the wipes are applied in pass 2.
-// The host engine (libs3topo.so) remains the executable specification: tests/test_gpu_topology.py compares whole tables.
+// The sequential procedure of the host engine (libs3topo.so) remains the executable specification, independent of the
+// core: tests/test_gpu_topology.py compares whole tables with it.
 #include "common.h"
 #include "scan_sort.h"
-#include "topo_tables.h"
-
+#include "topo_core.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <exception>
 #include <vector>
@@ -40,69 +40,11 @@ using s3topo::INVALID;
 using s3topo::LEAF;
 using s3topo::NbEntry;
 using s3topo::NodeRule;
-using s3topo::REF_BASE;
-
-namespace {
-
-// host copies of the decision tables (fixed shape: every child has N_RULES entries)
-const NodeRule H_RULES_2D[4][s3topo::N_RULES_2D] = S3_NODE_RULES_2D_INIT;
-const NodeRule H_RULES_3D[8][s3topo::N_RULES_3D] = S3_NODE_RULES_3D_INIT;
-const int H_DIR2[4][3] = {{-1, -1, 0}, {-1, 1, 0}, {1, 1, 0}, {1, -1, 0}};
-const int H_DIR3[8][3] = {{-1, -1, 1}, {-1, 1, 1}, {1, 1, 1}, {1, -1, 1}, {-1, -1, -1}, {-1, 1, -1}, {1, 1, -1}, {1, -1, -1}};
-const int H_PLANE[8][2] = {{-1, 0}, {-1, 1}, {0, 1}, {1, 1}, {1, 0}, {1, -1}, {0, -1}, {-1, -1}};
-
-void slot_offset(int slot, int o[3]) {
-    o[2] = 0;
-    if (slot < 8) { o[0] = H_PLANE[slot][0]; o[1] = H_PLANE[slot][1]; return; }
-    if (slot < 16) { o[0] = H_PLANE[slot - 8][0]; o[1] = H_PLANE[slot - 8][1]; o[2] = -1; return; }
-    if (slot == 16) { o[0] = 0; o[1] = 0; o[2] = -1; return; }
-    if (slot < 25) { o[0] = H_PLANE[slot - 17][0]; o[1] = H_PLANE[slot - 17][1]; o[2] = 1; return; }
-    o[0] = 0; o[1] = 0; o[2] = 1;
-}
-
-// lattice rule behind the reference's neighbour table (same construction as topology.cpp)
-std::vector<NbEntry> build_nb_table(int dim) {
-    const int nch = 1 << dim, nnb = dim == 2 ? 8 : 26;
-    std::vector<NbEntry> tab((size_t)nch * nnb);
-    for (int c = 0; c < nch; ++c)
-        for (int s = 0; s < nnb; ++s) {
-            int o[3], p[3] = {0, 0, 0}, big[3] = {0, 0, 0}, t[3] = {0, 0, 0};
-            slot_offset(s, o);
-            const int *dc = dim == 2 ? H_DIR2[c] : H_DIR3[c];
-            bool crosses = false;
-            for (int j = 0; j < dim; ++j) {
-                p[j] = dc[j] + 2 * o[j];
-                big[j] = p[j] == 3 ? 1 : (p[j] == -3 ? -1 : 0);
-                t[j] = p[j] - 4 * big[j];
-                crosses |= big[j] != 0;
-            }
-            int pslot = -1, target = -1;
-            if (crosses)
-                for (int q = 0; q < nnb; ++q) {
-                    int u[3];
-                    slot_offset(q, u);
-                    if (u[0] == big[0] && u[1] == big[1] && (dim == 2 || u[2] == big[2])) pslot = q;
-                }
-            for (int q = 0; q < nch; ++q) {
-                const int *d = dim == 2 ? H_DIR2[q] : H_DIR3[q];
-                if (d[0] == t[0] && d[1] == t[1] && (dim == 2 || d[2] == t[2])) target = q;
-            }
-            tab[(size_t)c * nnb + s] = NbEntry{(int8_t)pslot, (int8_t)target};
-        }
-    return tab;
-}
-
-}  // namespace
+using s3topo::TopoTables;
+using s3topo::child_row;
 
 // what the kernels see (by value)
-struct TopoView {
-    int dim, nch, nnb, n_rules;
-    int32_t *level, *parent, *first_child, *batch_pos, *nb;
-    int64_t *node_idx;
-    double *center, *nodes;
-    const NbEntry *nb_table;
-    const NodeRule *rules;           // [nch][n_rules]
-    const double *half_width, *quarter_width;
+struct TopoView : TopoTables {
     int64_t *counters;               // [0] nodes in use, [1] error flag, [2] min referenced node, [3] max, [4] scratch total
 };
 
@@ -143,13 +85,6 @@ namespace s3 {
 constexpr int TB = 128;
 static unsigned blocks_for(int64_t n) { return (unsigned)((n + TB - 1) / TB); }
 
-__device__ __forceinline__ int64_t enc_new(int local) { return -(int64_t)(1 + local); }
-__device__ __forceinline__ bool is_new(int64_t v) { return v < 0 && v > -REF_BASE; }
-__device__ __forceinline__ int dec_new(int64_t v) { return (int)(-v - 1); }
-__device__ __forceinline__ int64_t enc_ref(int64_t entry) { return -(REF_BASE + entry); }
-__device__ __forceinline__ bool is_ref(int64_t v) { return v <= -REF_BASE; }
-__device__ __forceinline__ int64_t dec_ref(int64_t v) { return -v - REF_BASE; }
-
 __global__ void topo_validate_kernel(TopoView t, const int64_t *__restrict__ parents, int64_t n, int64_t first) {
     const int64_t i = blockIdx.x * (int64_t)TB + threadIdx.x;
     if (i >= n) return;
@@ -158,117 +93,24 @@ __global__ void topo_validate_kernel(TopoView t, const int64_t *__restrict__ par
         atomicExch(reinterpret_cast<unsigned long long *>(&t.counters[1]), 1ull);
 }
 
-// row of child c of a cell whose row is `prow` and whose children start at fc (_assign_neighbors for one child);
-// fc_of(q) = first child of q as the caller sees it
-template <typename FcOf>
-__device__ __forceinline__ void child_row(const TopoView &t, const int32_t *prow, int32_t fc, int c, int32_t *out, FcOf fc_of) {
-    for (int s = 0; s < t.nnb; ++s) {
-        const NbEntry e = t.nb_table[c * t.nnb + s];
-        if (e.pslot < 0) { out[s] = fc + e.target; continue; }
-        const int32_t q = prow[e.pslot];
-        const int32_t f = q >= 0 ? fc_of(q) : -1;
-        out[s] = f >= 0 ? f + e.target : q;                    // parent_or_child, s_cube.py:1758-1775
-    }
-}
-
-// pass A of a refine batch: the children of parent i -- levels, centres, links, node entries (final id / l-th new node of
-// this parent / reference to an entry of an earlier parent's child); one thread per parent, as the sequential numbering
-// of a parent's new nodes asks for
+// pass A of a refine batch (s3topo::build_children); one thread per parent, as the sequential numbering of a parent's
+// new nodes asks for
 __global__ void __launch_bounds__(TB)
 topo_build_kernel(TopoView t, const int64_t *__restrict__ parents, int64_t n, int64_t first, int64_t *__restrict__ new_count) {
     const int64_t i = blockIdx.x * (int64_t)TB + threadIdx.x;
     if (i >= n || t.counters[1] != 0) return;
-    const int nch = t.nch, nnb = t.nnb, dim = t.dim;
-    const int32_t P = (int32_t)parents[i];
-    const int32_t fc = (int32_t)(first + i * nch);
-    const int32_t lvl = t.level[P] + 1;
-    const double off = t.quarter_width[lvl - 1];
-    for (int c = 0; c < nch; ++c) {
-        const size_t cell = (size_t)fc + c;
-        t.level[cell] = lvl;
-        t.parent[cell] = P;
-        t.first_child[cell] = LEAF;
-        t.batch_pos[cell] = -1;
-        for (int j = 0; j < dim; ++j) t.center[cell * dim + j] = t.center[(size_t)P * dim + j] + dir_comp(dim, c, j) * off;
-    }
-    // links: a neighbour of the parent counts as refined when it was before the batch or comes earlier in it
-    int32_t prow[26];
-    for (int s = 0; s < nnb; ++s) prow[s] = t.nb[(size_t)P * nnb + s];
-    auto fc_of = [&](int32_t q) {
-        int32_t f = t.first_child[q];
-        if (f == LEAF) {
-            const int32_t bp = t.batch_pos[q];
-            if (bp >= 0 && bp < i) f = (int32_t)(first + (int64_t)bp * nch);
-        }
-        return f;
-    };
-    for (int c = 0; c < nch; ++c) child_row(t, prow, fc, c, &t.nb[(size_t)(fc + c) * nnb], fc_of);
-    // node entries
-    int local = 0;
-    for (int k = 0; k < nch; ++k) {
-        const int32_t cell = fc + k;
-        int64_t *ni = &t.node_idx[(size_t)cell * nch];
-        const int32_t *cnb = &t.nb[(size_t)cell * nnb];
-        ni[k] = t.node_idx[(size_t)P * nch + k];
-        for (int ri = 0; ri < t.n_rules; ++ri) {
-            const NodeRule r = t.rules[k * t.n_rules + ri];
-            if (r.n_cand < 0) {
-                ni[r.node] = t.node_idx[(size_t)(fc + r.cand[0][0]) * nch + r.cand[0][1]];
-                continue;
-            }
-            bool found = false;
-            for (int a = 0; a < r.n_cand && !found; ++a) {
-                const int32_t q = cnb[r.cand[a][0]];
-                if (q < 0) continue;
-                const int64_t entry = (int64_t)q * nch + r.cand[a][1];
-                if (q >= first) {
-                    // a cell of this batch: a leaf by construction; its level is its parent's + 1
-                    const int64_t j = (q - first) / nch;
-                    if (t.level[parents[j]] + 1 != lvl) continue;
-                    ni[r.node] = j == i ? t.node_idx[entry] : enc_ref(entry);      // own sibling: entry as it stands
-                    found = true;
-                } else if (t.first_child[q] == LEAF && !(t.batch_pos[q] >= 0 && t.batch_pos[q] < i) && t.level[q] == lvl) {
-                    ni[r.node] = t.node_idx[entry];
-                    found = true;
-                }
-            }
-            if (!found) ni[r.node] = enc_new(local++);
-        }
-    }
-    new_count[i] = local;
+    new_count[i] = s3topo::build_children(t, i, parents, first);
 }
 
-// pass C: the parent's new nodes get their ids (in the order pass A met them) and their coordinates
+// pass C (s3topo::number_new_nodes)
 __global__ void __launch_bounds__(TB)
 topo_number_kernel(TopoView t, int64_t n, int64_t first, const int64_t *__restrict__ new_base) {
     const int64_t i = blockIdx.x * (int64_t)TB + threadIdx.x;
     if (i >= n || t.counters[1] != 0) return;
-    const int nch = t.nch, dim = t.dim;
-    const int32_t fc = (int32_t)(first + i * nch);
-    const int64_t base = t.counters[0] + new_base[i];
-    int seen = 0;
-    for (int k = 0; k < nch; ++k) {
-        const int32_t cell = fc + k;
-        int64_t *ni = &t.node_idx[(size_t)cell * nch];
-        auto fix = [&](int node) {
-            const int64_t v = ni[node];
-            if (!is_new(v)) return;
-            const int l = dec_new(v);
-            if (l == seen) {
-                const double off = t.half_width[t.level[cell]];
-                for (int j = 0; j < dim; ++j)
-                    t.nodes[(size_t)(base + l) * dim + j] = t.center[(size_t)cell * dim + j] + dir_comp(dim, node, j) * off;
-                ++seen;
-            }
-            ni[node] = base + l;
-        };
-        fix(k);
-        for (int ri = 0; ri < t.n_rules; ++ri) fix(t.rules[k * t.n_rules + ri].node);
-    }
+    s3topo::number_new_nodes(t, i, first, t.counters[0] + new_base[i]);
 }
 
-// pass D: follow references into earlier parents' children until a final id is met (a stale read sees an older link of
-// the same chain, never a wrong id)
+// pass D (s3topo::resolve_ref), one thread per node entry of the new cells; a chain that does not end raises the error flag
 __global__ void __launch_bounds__(TB)
 topo_resolve_kernel(TopoView t, int64_t n, int64_t first) {
     const int64_t e = blockIdx.x * (int64_t)TB + threadIdx.x;
@@ -277,11 +119,9 @@ topo_resolve_kernel(TopoView t, int64_t n, int64_t first) {
     volatile int64_t *tab = t.node_idx;
     const size_t at = (size_t)first * t.nch + (size_t)e;
     int64_t v = tab[at];
-    if (!is_ref(v)) return;
-    // a lattice point is shared by at most 2^d cells, so a chain has at most 2^d - 1 links; the bound is the exit every
-    // wave reaches whatever the tables hold
-    for (int hop = 0; hop < 64 && is_ref(v); ++hop) v = tab[(size_t)dec_ref(v)];
-    if (is_ref(v)) {
+    if (!s3topo::is_ref(v)) return;
+    v = s3topo::resolve_ref([&](int64_t entry) { return tab[(size_t)entry]; }, v);
+    if (s3topo::is_ref(v)) {
         atomicExch(reinterpret_cast<unsigned long long *>(&t.counters[1]), 2ull);
         return;
     }
@@ -311,7 +151,7 @@ topo_relink_batch_kernel(TopoView t, const int64_t *__restrict__ parents, int64_
     if (fc < 0) return;
     int32_t prow[26];
     for (int s = 0; s < t.nnb; ++s) prow[s] = t.nb[(size_t)P * t.nnb + s];
-    child_row(t, prow, fc, c, &t.nb[(size_t)(fc + c) * t.nnb], [&](int32_t q) { return t.first_child[q]; });
+    child_row(t, prow, fc, c, &t.nb[(size_t)(fc + c) * t.nnb], [&](int32_t q, int) { return t.first_child[q]; });
 }
 
 // ---- relink_parent_of(cells): ordered refreshes of the listed cells' parents -----------------------------------------
@@ -360,7 +200,7 @@ topo_relink_compute_kernel(TopoView t, const int64_t *__restrict__ cells, int64_
     // the row of `a` is still the one in the table; come back down
     int32_t row[26], next[26];
     for (int s = 0; s < nnb; ++s) row[s] = t.nb[(size_t)a * nnb + s];
-    auto fc_of = [&](int32_t q) { return t.first_child[q]; };
+    auto fc_of = [&](int32_t q, int) { return t.first_child[q]; };
     while (depth > 0) {
         const int c = path[--depth];
         child_row(t, row, t.first_child[a], c, next, fc_of);
@@ -639,17 +479,16 @@ int s3_topo_create(int dim, double width, const double *h_root_center, s3_topo *
         }                                                                                              \
     } while (0)
     S3_TOPO_TRY(hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking));
-    const std::vector<NbEntry> tab = build_nb_table(dim);
-    S3_TOPO_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_nb_table), tab.size() * sizeof(NbEntry)));
-    S3_TOPO_TRY(hipMemcpy(t->d_nb_table, tab.data(), tab.size() * sizeof(NbEntry), hipMemcpyHostToDevice));
+    NbEntry tab[8 * 26];
+    s3topo::build_nb_table(dim, tab);
+    const size_t tab_bytes = sizeof(NbEntry) * (size_t)t->nch * t->nnb;
+    S3_TOPO_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_nb_table), tab_bytes));
+    S3_TOPO_TRY(hipMemcpy(t->d_nb_table, tab, tab_bytes, hipMemcpyHostToDevice));
     const size_t rule_bytes = sizeof(NodeRule) * (size_t)t->nch * t->n_rules;
     S3_TOPO_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_rules), rule_bytes));
-    S3_TOPO_TRY(hipMemcpy(t->d_rules, dim == 2 ? (const void *)H_RULES_2D : (const void *)H_RULES_3D, rule_bytes, hipMemcpyHostToDevice));
+    S3_TOPO_TRY(hipMemcpy(t->d_rules, dim == 2 ? (const void *)s3topo::NODE_RULES_2D : (const void *)s3topo::NODE_RULES_3D, rule_bytes, hipMemcpyHostToDevice));
     double widths[128];
-    for (int l = 0; l < 64; ++l) {
-        widths[l] = (0.5 * width) / std::ldexp(1.0, l);            // half_width, as topology.cpp
-        widths[64 + l] = (0.25 * width) / std::ldexp(1.0, l);      // quarter_width
-    }
+    s3topo::fill_level_widths(width, widths, widths + 64);
     S3_TOPO_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_widths), sizeof(widths)));
     S3_TOPO_TRY(hipMemcpy(t->d_widths, widths, sizeof(widths), hipMemcpyHostToDevice));
     S3_TOPO_TRY(hipMalloc(reinterpret_cast<void **>(&t->counters), 8 * sizeof(int64_t)));
@@ -668,8 +507,7 @@ int s3_topo_create(int dim, double width, const double *h_root_center, s3_topo *
     std::vector<double> nodes((size_t)t->nch * dim);
     for (int c = 0; c < t->nch; ++c) {
         ni[c] = c;
-        const int *d = dim == 2 ? H_DIR2[c] : H_DIR3[c];
-        for (int j = 0; j < dim; ++j) nodes[(size_t)c * dim + j] = h_root_center[j] + d[j] * 0.5 * width;
+        for (int j = 0; j < dim; ++j) nodes[(size_t)c * dim + j] = h_root_center[j] + s3topo::dir_comp(c, j) * 0.5 * width;
     }
     const int32_t zero = 0, minus1 = -1, leaf = LEAF;
     const int64_t counters[8] = {t->nch, 0, INT64_MAX, -1, 0, 0, 0, 0};

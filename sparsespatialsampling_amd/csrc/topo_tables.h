@@ -1,4 +1,5 @@
-// Decision tables of the S^3 topology shared by the host engine (topology.cpp) and the device engine (topo_dev.hip).
+// Decision tables of the S^3 topology: one instance, read by the per-parent core (topo_core.h) that the host engine
+// (topology.cpp) and the device engine (topo_dev.hip) both instantiate, and by the host engine's sequential procedure.
 //
 // Reference behaviour: _assign_indices, s_cube.py:1188-1536 (which node of a new child is taken from which same-level
 // leaf neighbour / earlier sibling, in which order), restated as tables; s3t_selfcheck (topology.cpp) verifies them
@@ -50,7 +51,11 @@ struct NbEntry { int8_t pslot; int8_t target; };   // pslot < 0: sibling `target
                    {5, -1, {{4, 6}}}, {6, -1, {{6, 7}}}}, \
 }
 
-// transient encodings of a node id while a batch is assembled in parallel (final ids are >= 0)
+// fixed shape: every child has N_RULES entries.  The host engine indexes them, the device engine uploads them
+inline constexpr NodeRule NODE_RULES_2D[4][N_RULES_2D] = S3_NODE_RULES_2D_INIT;
+inline constexpr NodeRule NODE_RULES_3D[8][N_RULES_3D] = S3_NODE_RULES_3D_INIT;
+
+// transient encodings of a node id while a batch is assembled in parallel (final ids are >= 0), topo_core.h
 constexpr int64_t REF_BASE = (int64_t)1 << 20;
 
 }  // namespace s3topo

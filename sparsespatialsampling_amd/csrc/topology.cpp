@@ -1,10 +1,16 @@
 // Host-side topology engine of the S^3 sampling tree (plain C++, no GPU): neighbour links, shared-node numbering and
 // the final renumbering, with the reference's *sequential* semantics.
 //
+// Two forms of a refine batch live here.  The sequential procedure (refine_one -> assign_neighbors / assign_indices /
+// check_nb_node / new_node) restates the reference's _assign_indices cell by cell and is independent of everything
+// else.  The batch form (refine_batch_parallel) runs the per-parent core of topo_core.h on a thread pool -- the same
+// source the kernels of the device engine (topo_dev.hip) instantiate -- and is judged by the sequential procedure
+// (tests/test_topology_parallel.py).
+//
 // Reference behaviour restated here (file:line relative to the reference checkout):
 //   Cell                         s_cube.py:32-83      -> structure-of-arrays (level, parent, first_child, nb, node_idx)
-//   _assign_neighbors            s_cube.py:904-1186   -> generated from the lattice rule (see build_nb_table)
-//   _assign_indices              s_cube.py:1188-1536  -> NODE_RULES_2D / NODE_RULES_3D decision tables
+//   _assign_neighbors            s_cube.py:904-1186   -> generated from the lattice rule (topo_core.h, build_nb_table)
+//   _assign_indices              s_cube.py:1188-1536  -> NODE_RULES_2D / NODE_RULES_3D decision tables (topo_tables.h)
 //   check_nb_node                s_cube.py:1739-1755
 //   _remove_invalid_cells (nb)   s_cube.py:721-728
 //   _check_nb                    s_cube.py:447-464
@@ -17,7 +23,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdlib>
@@ -28,7 +33,7 @@
 #include <thread>
 #include <vector>
 
-#include "topo_tables.h"
+#include "topo_core.h"
 
 namespace {
 
@@ -36,44 +41,9 @@ using s3topo::INVALID;
 using s3topo::LEAF;
 using s3topo::NbEntry;
 using s3topo::NodeRule;
-using s3topo::REF_BASE;
-
-// child / node directions, s_cube.py:188-194
-const int DIR2[4][3] = {{-1, -1, 0}, {-1, 1, 0}, {1, 1, 0}, {1, -1, 0}};
-const int DIR3[8][3] = {{-1, -1, 1}, {-1, 1, 1}, {1, 1, 1}, {1, -1, 1}, {-1, -1, -1}, {-1, 1, -1}, {1, 1, -1}, {1, -1, -1}};
-
-// neighbour slots, s_cube.py:22-26: in-plane order w, nw, n, ne, e, se, s, sw; 0-7 same plane, 8-15 lower plane,
-// 16 = directly below, 17-24 upper plane, 25 = directly above
-const int PLANE[8][2] = {{-1, 0}, {-1, 1}, {0, 1}, {1, 1}, {1, 0}, {1, -1}, {0, -1}, {-1, -1}};
-
-void slot_offset(int dim, int slot, int o[3]) {
-    o[2] = 0;
-    if (slot < 8) { o[0] = PLANE[slot][0]; o[1] = PLANE[slot][1]; return; }
-    (void)dim;
-    if (slot < 16) { o[0] = PLANE[slot - 8][0]; o[1] = PLANE[slot - 8][1]; o[2] = -1; return; }
-    if (slot == 16) { o[0] = 0; o[1] = 0; o[2] = -1; return; }
-    if (slot < 25) { o[0] = PLANE[slot - 17][0]; o[1] = PLANE[slot - 17][1]; o[2] = 1; return; }
-    o[0] = 0; o[1] = 0; o[2] = 1;
-}
-
-int offset_slot(int dim, const int o[3]) {
-    int nnb = dim == 2 ? 8 : 26;
-    for (int s = 0; s < nnb; ++s) {
-        int t[3];
-        slot_offset(dim, s, t);
-        if (t[0] == o[0] && t[1] == o[1] && (dim == 2 || t[2] == o[2])) return s;
-    }
-    return -1;
-}
-
-int dir_child(int dim, const int d[3]) {
-    int nch = 1 << dim;
-    for (int c = 0; c < nch; ++c) {
-        const int *t = dim == 2 ? DIR2[c] : DIR3[c];
-        if (t[0] == d[0] && t[1] == d[1] && (dim == 2 || t[2] == d[2])) return c;
-    }
-    return -1;
-}
+using s3topo::TopoTables;
+using s3topo::dir_comp;
+using s3topo::slot_offset;
 
 // minimal fork-join pool: run(n, grain, fn) calls fn(begin, end) over [0, n) in chunks of `grain` on the pool's threads
 // and the caller; returns when every chunk is done
@@ -144,14 +114,6 @@ struct Pool {
     }
 };
 
-// transient encodings of a node id while a batch is assembled in parallel (final ids are >= 0)
-inline int64_t enc_new(int local) { return -(int64_t)(1 + local); }                      // l-th new node of this parent
-inline bool is_new(int64_t v) { return v < 0 && v > -REF_BASE; }
-inline int dec_new(int64_t v) { return (int)(-v - 1); }
-inline int64_t enc_ref(int64_t entry) { return -(REF_BASE + entry); }                     // entry = cell * nch + node
-inline bool is_ref(int64_t v) { return v <= -REF_BASE; }
-inline int64_t dec_ref(int64_t v) { return -v - REF_BASE; }
-
 // growable table without value initialisation: growth is a realloc (for tables of this size an address-space remap, no
 // copy) and the new part is first touched by whichever thread fills it
 template <typename T>
@@ -176,9 +138,6 @@ struct Buf {
     const T *data() const { return p; }
 };
 
-const std::vector<NodeRule> NODE_RULES_2D[4] = S3_NODE_RULES_2D_INIT;
-const std::vector<NodeRule> NODE_RULES_3D[8] = S3_NODE_RULES_3D_INIT;
-
 struct Topo {
     int dim, nch, nnb;
     double width;
@@ -189,7 +148,8 @@ struct Topo {
     Buf<double> nodes;                // [n_nodes][dim]
     int64_t n_nodes_used = 0;
     size_t cell_cap = 0;              // cells the cell tables have room for
-    std::vector<NbEntry> nb_table;    // [nch][nnb]
+    NbEntry nb_table[8 * 26];         // [nch][nnb], s3topo::build_nb_table
+    TopoTables view;                  // the tables as the per-parent core (topo_core.h) takes them: refresh_view()
     // finalize() results
     std::vector<int64_t> face_ids;    // after finalize(): old node id -> new node id (-1 = dropped)
     int64_t n_leaf = 0, n_unique = 0;
@@ -200,36 +160,14 @@ struct Topo {
 
     int64_t n_cells() const { return n_used; }
     int64_t n_nodes() const { return n_nodes_used; }
-    const int *dir(int c) const { return dim == 2 ? DIR2[c] : DIR3[c]; }
-
-    // lattice rule behind the reference's hand-written neighbour table (verified against the reference's tables,
-    // SURVEY.md 8(a) a10): child direction dc, slot offset o, p = dc + 2o; |p_j| == 3 -> crosses into the parent's
-    // neighbour in that direction
-    void build_nb_table() {
-        nb_table.assign((size_t)nch * nnb, NbEntry{-1, -1});
-        for (int c = 0; c < nch; ++c)
-            for (int s = 0; s < nnb; ++s) {
-                int o[3], p[3] = {0, 0, 0}, big[3] = {0, 0, 0}, t[3] = {0, 0, 0};
-                slot_offset(dim, s, o);
-                bool crosses = false;
-                for (int j = 0; j < dim; ++j) {
-                    p[j] = dir(c)[j] + 2 * o[j];
-                    big[j] = p[j] == 3 ? 1 : (p[j] == -3 ? -1 : 0);
-                    t[j] = p[j] - 4 * big[j];
-                    crosses |= big[j] != 0;
-                }
-                NbEntry e;
-                e.pslot = crosses ? (int8_t)offset_slot(dim, big) : (int8_t)-1;
-                e.target = (int8_t)dir_child(dim, t);
-                nb_table[(size_t)c * nnb + s] = e;
-            }
-    }
+    const NodeRule *rules_of(int child) const { return view.rules + child * view.n_rules; }
 
     void push_cell(int32_t lvl, int32_t par, const double *c) {
         const size_t i = (size_t)n_used++;
         level[i] = lvl;
         parent[i] = par;
         first_child[i] = LEAF;
+        batch_pos[i] = -1;
         for (int s = 0; s < nnb; ++s) nb[i * nnb + s] = -1;
         for (int s = 0; s < nch; ++s) node_idx[i * nch + s] = 0;
         for (int j = 0; j < dim; ++j) center[i * dim + j] = c[j];
@@ -240,39 +178,35 @@ struct Topo {
     void reserve_cells(int64_t extra) {
         const size_t want = (size_t)(n_cells() + extra);
         nodes.grow((size_t)(n_nodes_used + extra * nch) * dim);
-        if (want <= cell_cap) return;
-        const size_t cap = std::max<size_t>(std::max(want, cell_cap * 2), 1024);
-        level.grow(cap);
-        parent.grow(cap);
-        first_child.grow(cap);
-        nb.grow(cap * nnb);
-        node_idx.grow(cap * nch);
-        center.grow(cap * dim);
-        const size_t old = batch_pos.cap;
-        batch_pos.grow(cap);
-        for (size_t i = old; i < batch_pos.cap; ++i) batch_pos[i] = -1;
-        cell_cap = cap;
+        if (want > cell_cap) {
+            const size_t cap = std::max<size_t>(std::max(want, cell_cap * 2), 1024);
+            level.grow(cap);
+            parent.grow(cap);
+            first_child.grow(cap);
+            nb.grow(cap * nnb);
+            node_idx.grow(cap * nch);
+            center.grow(cap * dim);
+            batch_pos.grow(cap);
+            cell_cap = cap;
+        }
+        refresh_view();
+    }
+    // (the sequential procedure grows `nodes` on its own, node by node: every batch of the core starts with reserve_cells)
+    void refresh_view() {
+        view.level = level.data(), view.parent = parent.data(), view.first_child = first_child.data();
+        view.batch_pos = batch_pos.data(), view.nb = nb.data(), view.node_idx = node_idx.data();
+        view.center = center.data(), view.nodes = nodes.data();
     }
 
     // _assign_neighbors(cell, children=existing children)
     void assign_neighbors(int32_t P) {
         const int32_t fc = first_child[P];
         if (fc < 0) return;
-        const int32_t *pnb = &nb[(size_t)P * nnb];
-        int32_t q_of[26], fc_of[26];                                   // the parent's neighbours and their first child
-        for (int s = 0; s < nnb; ++s) {
-            q_of[s] = pnb[s];
-            fc_of[s] = q_of[s] >= 0 ? first_child[q_of[s]] : -1;
-        }
-        const NbEntry *tab = nb_table.data();
-        for (int c = 0; c < nch; ++c) {
-            int32_t *cnb = &nb[(size_t)(fc + c) * nnb];
-            for (int s = 0; s < nnb; ++s) {
-                const NbEntry e = tab[c * nnb + s];
-                if (e.pslot < 0) { cnb[s] = fc + e.target; continue; }
-                cnb[s] = fc_of[e.pslot] >= 0 ? fc_of[e.pslot] + e.target : q_of[e.pslot];     // parent_or_child
-            }
-        }
+        const int32_t *prow = &nb[(size_t)P * nnb];
+        int32_t frow[26];                                              // first child of every neighbour of the parent
+        for (int s = 0; s < nnb; ++s) frow[s] = prow[s] >= 0 ? first_child[prow[s]] : -1;
+        for (int c = 0; c < nch; ++c)
+            s3topo::child_row(view, prow, fc, c, &nb[(size_t)(fc + c) * nnb], [&](int32_t, int slot) { return frow[slot]; });
     }
 
     bool check_nb_node(int32_t cell, int slot) const {
@@ -283,7 +217,7 @@ struct Topo {
     int64_t new_node(int32_t cell, int node) {
         const double off = half_width[level[cell]];
         nodes.grow((size_t)(n_nodes_used + 1) * dim);
-        for (int j = 0; j < dim; ++j) nodes[(size_t)n_nodes_used * dim + j] = center[(size_t)cell * dim + j] + dir(node)[j] * off;
+        for (int j = 0; j < dim; ++j) nodes[(size_t)n_nodes_used * dim + j] = center[(size_t)cell * dim + j] + dir_comp(node, j) * off;
         return n_nodes_used++;
     }
 
@@ -294,8 +228,9 @@ struct Topo {
             const int32_t cell = fc + i;
             int64_t *ni = &node_idx[(size_t)cell * nch];
             ni[i] = node_idx[(size_t)P * nch + i];
-            const std::vector<NodeRule> &rules = dim == 2 ? NODE_RULES_2D[i] : NODE_RULES_3D[i];
-            for (const NodeRule &r : rules) {
+            const NodeRule *rules = rules_of(i);
+            for (int ri = 0; ri < view.n_rules; ++ri) {
+                const NodeRule &r = rules[ri];
                 if (r.n_cand < 0) {
                     ni[r.node] = node_idx[(size_t)(fc + r.cand[0][0]) * nch + r.cand[0][1]];
                     continue;
@@ -312,13 +247,7 @@ struct Topo {
     }
 
     // ---- a whole batch at once, on several threads, with the result of the sequential procedure ------------------
-    // Sequentially, parent i sees the parents before it in the batch as refined and their children as existing leaves,
-    // and new node ids are handed out in processing order.  Because the ids of the children are known up front
-    // (first + 2^d * position) all of that can be evaluated per parent from the state before the batch plus the
-    // position table: pass A builds the children of every parent independently (links; node entries as final id /
-    // l-th new node of this parent / reference to an entry of an earlier parent's child), an exclusive scan of the
-    // new-node counts gives every parent its id range, pass C turns "l-th new node" into ids and writes the
-    // coordinates, pass D follows the references (a lattice point is shared by at most 2^d cells: short chains).
+    // The per-parent passes A, C and D are the core of topo_core.h, which the kernels of the device engine instantiate too.
     Buf<int32_t> batch_pos;              // cell -> position in the current batch, -1 otherwise (sized with the cell tables)
     std::vector<int32_t> new_count;      // per parent of the batch: nodes it creates
     std::vector<int64_t> new_base;       // exclusive scan of new_count
@@ -329,113 +258,6 @@ struct Topo {
     double phase_s[12] = {0};
     static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
     int64_t par_min = 64;                // smaller batches take the sequential procedure (S3_TOPO_PAR_MIN)
-
-    const std::vector<NodeRule> &rules_of(int child) const { return dim == 2 ? NODE_RULES_2D[child] : NODE_RULES_3D[child]; }
-
-    void build_children(int64_t i, const int64_t *parents, int64_t first) {
-        const int32_t P = (int32_t)parents[i];
-        const int32_t fc = (int32_t)(first + i * nch);
-        const int32_t lvl = level[P] + 1;
-        const double off = quarter_width[level[P]];
-        for (int c = 0; c < nch; ++c) {
-            const size_t cell = (size_t)fc + c;
-            level[cell] = lvl;
-            parent[cell] = P;
-            first_child[cell] = LEAF;
-            for (int j = 0; j < dim; ++j) center[cell * dim + j] = center[(size_t)P * dim + j] + dir(c)[j] * off;
-            for (int m = 0; m < nch; ++m) node_idx[cell * nch + m] = 0;
-        }
-        // links: a neighbour of the parent counts as refined when it was before the batch or comes earlier in it
-        const int32_t *pnb = &nb[(size_t)P * nnb];
-        int32_t q_of[26], fc_of[26];
-        for (int s = 0; s < nnb; ++s) {
-            const int32_t q = pnb[s];
-            int32_t f = -1;
-            if (q >= 0) {
-                f = first_child[q];
-                if (f == LEAF && batch_pos[q] >= 0 && batch_pos[q] < i) f = (int32_t)(first + (int64_t)batch_pos[q] * nch);
-            }
-            q_of[s] = q;
-            fc_of[s] = f;
-        }
-        const NbEntry *tab = nb_table.data();
-        for (int c = 0; c < nch; ++c) {
-            int32_t *cnb = &nb[(size_t)(fc + c) * nnb];
-            for (int s = 0; s < nnb; ++s) {
-                const NbEntry e = tab[c * nnb + s];
-                if (e.pslot < 0) { cnb[s] = fc + e.target; continue; }
-                cnb[s] = fc_of[e.pslot] >= 0 ? fc_of[e.pslot] + e.target : q_of[e.pslot];
-            }
-        }
-        // node entries
-        int local = 0;
-        for (int k = 0; k < nch; ++k) {
-            const int32_t cell = fc + k;
-            int64_t *ni = &node_idx[(size_t)cell * nch];
-            const int32_t *cnb = &nb[(size_t)cell * nnb];
-            ni[k] = node_idx[(size_t)P * nch + k];
-            for (const NodeRule &r : rules_of(k)) {
-                if (r.n_cand < 0) {
-                    ni[r.node] = node_idx[(size_t)(fc + r.cand[0][0]) * nch + r.cand[0][1]];
-                    continue;
-                }
-                bool found = false;
-                for (int a = 0; a < r.n_cand && !found; ++a) {
-                    const int32_t q = cnb[r.cand[a][0]];
-                    if (q < 0) continue;
-                    const int64_t entry = (int64_t)q * nch + r.cand[a][1];
-                    if (q >= first) {
-                        // a cell of this batch: a leaf by construction; its level is its parent's + 1
-                        const int64_t j = (q - first) / nch;
-                        if (level[parents[j]] + 1 != lvl) continue;
-                        ni[r.node] = j == i ? node_idx[entry] : enc_ref(entry);      // own sibling: entry as it stands
-                        found = true;
-                    } else if (first_child[q] == LEAF && !(batch_pos[q] >= 0 && batch_pos[q] < i) && level[q] == lvl) {
-                        ni[r.node] = node_idx[entry];
-                        found = true;
-                    }
-                }
-                if (!found) ni[r.node] = enc_new(local++);
-            }
-        }
-        new_count[i] = local;
-    }
-
-    // pass C: the parent's new nodes get their ids (in the order pass A met them) and their coordinates
-    void number_new_nodes(int64_t i, int64_t first, int64_t nodes_before) {
-        const int32_t fc = (int32_t)(first + i * nch);
-        const int64_t base = nodes_before + new_base[i];
-        int seen = 0;
-        for (int k = 0; k < nch; ++k) {
-            const int32_t cell = fc + k;
-            int64_t *ni = &node_idx[(size_t)cell * nch];
-            auto fix = [&](int node) {
-                const int64_t v = ni[node];
-                if (!is_new(v)) return;
-                const int l = dec_new(v);
-                if (l == seen) {
-                    const double off = half_width[level[cell]];
-                    for (int j = 0; j < dim; ++j)
-                        nodes[(size_t)(base + l) * dim + j] = center[(size_t)cell * dim + j] + dir(node)[j] * off;
-                    ++seen;
-                }
-                ni[node] = base + l;
-            };
-            fix(k);
-            for (const NodeRule &r : rules_of(k)) fix(r.node);
-        }
-    }
-
-    // pass D: follow references into earlier parents' children until a final id is met
-    void resolve_refs(int64_t i, int64_t first) {
-        int64_t *ni = &node_idx[(size_t)(first + i * nch) * nch];
-        for (int e = 0; e < nch * nch; ++e) {
-            int64_t v = ni[e];
-            if (!is_ref(v)) continue;
-            while (is_ref(v)) v = __atomic_load_n(&node_idx[(size_t)dec_ref(v)], __ATOMIC_RELAXED);
-            __atomic_store_n(&ni[e], v, __ATOMIC_RELAXED);
-        }
-    }
 
     void prefetch_parent(int32_t P) const {
         const int32_t *row = &nb[(size_t)P * nnb];
@@ -470,7 +292,8 @@ struct Topo {
         }
     }
 
-    // returns the id of the first new cell, -1 if a parent is not a leaf (or listed twice)
+    // returns the id of the first new cell, -1 if a parent is not a leaf (or listed twice), -3 if a node reference of
+    // pass D does not end (the tables are then as before the batch)
     int64_t refine_batch_parallel(const int64_t *parents, int64_t n, int relink) {
         const int64_t first = n_cells(), nodes_before = n_nodes();
         double t0 = now(), t1;
@@ -495,7 +318,7 @@ struct Topo {
                 if (i + 4 < e) prefetch_parent((int32_t)parents[i + 4]);
                 if (i + 2 < e) prefetch_neighbours((int32_t)parents[i + 2]);
                 if (i + 1 < e) prefetch_neighbour_children((int32_t)parents[i + 1]);
-                build_children(i, parents, first);
+                new_count[i] = s3topo::build_children(view, i, parents, first);
             }
         });
         t1 = now(); phase_s[1] += t1 - t0; t0 = t1;
@@ -505,16 +328,29 @@ struct Topo {
             total += new_count[i];
         }
         nodes.grow((size_t)(nodes_before + total) * dim);
-        n_nodes_used = nodes_before + total;
+        refresh_view();
         t1 = now(); phase_s[2] += t1 - t0; t0 = t1;
         pool->run(n, 512, [&](int64_t b, int64_t e) {
-            for (int64_t i = b; i < e; ++i) number_new_nodes(i, first, nodes_before);
+            for (int64_t i = b; i < e; ++i) s3topo::number_new_nodes(view, i, first, nodes_before + new_base[i]);
         });
         t1 = now(); phase_s[3] += t1 - t0; t0 = t1;
-        pool->run(n, 512, [&](int64_t b, int64_t e) {
-            for (int64_t i = b; i < e; ++i) resolve_refs(i, first);
+        int unresolved = 0;
+        int64_t *tab = node_idx.data();
+        const auto load = [tab](int64_t entry) { return __atomic_load_n(&tab[entry], __ATOMIC_RELAXED); };
+        pool->run(n * nch * nch, 512 * nch * nch, [&](int64_t b, int64_t e) {
+            for (int64_t at = first * nch + b; at < first * nch + e; ++at) {
+                if (!s3topo::is_ref(tab[at])) continue;
+                const int64_t v = s3topo::resolve_ref(load, tab[at]);
+                if (s3topo::is_ref(v)) __atomic_store_n(&unresolved, 1, __ATOMIC_RELAXED);
+                __atomic_store_n(&tab[at], v, __ATOMIC_RELAXED);
+            }
         });
         t1 = now(); phase_s[4] += t1 - t0; t0 = t1;
+        if (unresolved) {
+            for (int64_t i = 0; i < n; ++i) batch_pos[parents[i]] = -1;
+            return -3;
+        }
+        n_nodes_used = nodes_before + total;
         for (int64_t i = 0; i < n; ++i) {
             first_child[parents[i]] = (int32_t)(first + i * nch);
             batch_pos[parents[i]] = -1;
@@ -569,7 +405,7 @@ struct Topo {
         const double off = quarter_width[level[P]];
         for (int c = 0; c < nch; ++c) {
             double x[3];
-            for (int j = 0; j < dim; ++j) x[j] = center[(size_t)P * dim + j] + dir(c)[j] * off;
+            for (int j = 0; j < dim; ++j) x[j] = center[(size_t)P * dim + j] + dir_comp(c, j) * off;
             push_cell(level[P] + 1, P, x);
         }
         first_child[P] = fc;
@@ -591,11 +427,11 @@ void *s3t_create(int dim, double width, const double *root_center) try {
     t->nch = 1 << dim;
     t->nnb = dim == 2 ? 8 : 26;
     t->width = width;
-    t->build_nb_table();
-    for (int l = 0; l < 64; ++l) {
-        t->half_width[l] = (0.5 * width) / std::ldexp(1.0, l);
-        t->quarter_width[l] = (0.25 * width) / std::ldexp(1.0, l);
-    }
+    s3topo::build_nb_table(dim, t->nb_table);
+    s3topo::fill_level_widths(width, t->half_width, t->quarter_width);
+    const NodeRule *rules = dim == 2 ? &s3topo::NODE_RULES_2D[0][0] : &s3topo::NODE_RULES_3D[0][0];
+    t->view = TopoTables{dim, t->nch, t->nnb, dim == 2 ? s3topo::N_RULES_2D : s3topo::N_RULES_3D, nullptr, nullptr, nullptr, nullptr,
+                         nullptr, nullptr, nullptr, nullptr, t->nb_table, rules, t->half_width, t->quarter_width};
     t->reserve_cells(1);
     t->push_cell(0, -1, root_center);
     {
@@ -610,7 +446,7 @@ void *s3t_create(int dim, double width, const double *root_center) try {
     }
     // root nodes, s_cube.py:368,386-394: centre + dir * 0.5 * width, ids 0..2^d-1
     for (int c = 0; c < t->nch; ++c) {
-        for (int j = 0; j < dim; ++j) t->nodes[(size_t)c * dim + j] = root_center[j] + t->dir(c)[j] * 0.5 * width;
+        for (int j = 0; j < dim; ++j) t->nodes[(size_t)c * dim + j] = root_center[j] + dir_comp(c, j) * 0.5 * width;
         t->node_idx[c] = c;
     }
     t->n_nodes_used = t->nch;
@@ -648,43 +484,16 @@ static int64_t refine_batch(Topo *t, const int64_t *parents, int64_t n, int reli
 static int64_t refine_batch_sequential(Topo *t, const int64_t *parents, int64_t n, int relink) {
     const int64_t first = t->n_cells();
     t->reserve_cells(n * t->nch);
-    // the work per parent is a few dozen dependent look-ups in tables far larger than the caches; two software
-    // prefetch stages run ahead of it: the neighbour row of the parent four positions ahead, and -- once that row is
-    // there -- the entries of those neighbours two positions ahead
+    // the work per parent is a few dozen dependent look-ups in tables far larger than the caches; three software
+    // prefetch stages run ahead of it: the neighbour row of the parent four positions ahead, once that row is there the
+    // entries of those neighbours two positions ahead, and where a neighbour is refined already its children (what the
+    // new cells link to and share nodes with) one position ahead
     const int64_t n_before = t->n_cells();
     auto valid = [&](int64_t i) { return i < n && parents[i] >= 0 && parents[i] < n_before; };
     for (int64_t i = 0; i < n; ++i) {
-        if (valid(i + 4)) {
-            const int32_t *row = &t->nb[(size_t)parents[i + 4] * t->nnb];
-            __builtin_prefetch(row);
-            __builtin_prefetch(row + 16);
-            __builtin_prefetch(&t->node_idx[(size_t)parents[i + 4] * t->nch]);
-            __builtin_prefetch(&t->center[(size_t)parents[i + 4] * t->dim]);
-        }
-        if (valid(i + 2)) {
-            const int32_t *row = &t->nb[(size_t)parents[i + 2] * t->nnb];
-            for (int s_ = 0; s_ < t->nnb; ++s_) {
-                const int32_t q = row[s_];
-                if (q < 0) continue;
-                __builtin_prefetch(&t->first_child[q]);
-                __builtin_prefetch(&t->level[q]);
-                __builtin_prefetch(&t->node_idx[(size_t)q * t->nch]);
-            }
-        }
-        if (valid(i + 1)) {
-            // third stage: where a neighbour is refined already, its children are what the new cells link to and share
-            // nodes with
-            const int32_t *row = &t->nb[(size_t)parents[i + 1] * t->nnb];
-            for (int s_ = 0; s_ < t->nnb; ++s_) {
-                const int32_t q = row[s_];
-                if (q < 0) continue;
-                const int32_t fc = t->first_child[q];
-                if (fc < 0) continue;
-                __builtin_prefetch(&t->first_child[fc]);
-                __builtin_prefetch(&t->level[fc]);
-                for (int c = 0; c < t->nch; ++c) __builtin_prefetch(&t->node_idx[(size_t)(fc + c) * t->nch]);
-            }
-        }
+        if (valid(i + 4)) t->prefetch_parent((int32_t)parents[i + 4]);
+        if (valid(i + 2)) t->prefetch_neighbours((int32_t)parents[i + 2]);
+        if (valid(i + 1)) t->prefetch_neighbour_children((int32_t)parents[i + 1]);
         if (parents[i] < 0 || parents[i] >= t->n_cells() || t->first_child[parents[i]] != LEAF) return -1;
         t->refine_one((int32_t)parents[i]);
     }
@@ -1001,29 +810,26 @@ void s3t_gather_cells(void *h, const int64_t *ids, int64_t n, double *centers_ou
 // same lattice point as the node it supplies.  Returns the number of inconsistent entries (0 expected).
 int s3t_selfcheck(int dim) {
     int bad = 0;
-    const int nch = 1 << dim;
+    const int nch = 1 << dim, n_rules = dim == 2 ? s3topo::N_RULES_2D : s3topo::N_RULES_3D;
+    auto dir = [](int c, int j) { return (int)dir_comp(c, j); };
     for (int i = 0; i < nch; ++i) {
-        const int *di = dim == 2 ? DIR2[i] : DIR3[i];
-        const std::vector<NodeRule> &rules = dim == 2 ? NODE_RULES_2D[i] : NODE_RULES_3D[i];
+        const NodeRule *rules = dim == 2 ? s3topo::NODE_RULES_2D[i] : s3topo::NODE_RULES_3D[i];
         std::vector<int> seen(nch, 0);
         seen[i] = 1;
-        for (const NodeRule &r : rules) {
-            const int *dn = dim == 2 ? DIR2[r.node] : DIR3[r.node];
+        for (int ri = 0; ri < n_rules; ++ri) {
+            const NodeRule &r = rules[ri];
             seen[r.node] += 1;
             if (r.n_cand < 0) {
                 const int sib = r.cand[0][0], sn = r.cand[0][1];
-                const int *ds = dim == 2 ? DIR2[sib] : DIR3[sib];
-                const int *dsn = dim == 2 ? DIR2[sn] : DIR3[sn];
                 if (sib >= i) ++bad;
                 for (int j = 0; j < dim; ++j)
-                    if (di[j] + dn[j] != ds[j] + dsn[j]) { ++bad; break; }           // positions in quarter parent widths
+                    if (dir(i, j) + dir(r.node, j) != dir(sib, j) + dir(sn, j)) { ++bad; break; }   // positions in quarter parent widths
             } else {
                 for (int a = 0; a < r.n_cand; ++a) {
                     int o[3];
-                    slot_offset(dim, r.cand[a][0], o);
-                    const int *dq = dim == 2 ? DIR2[r.cand[a][1]] : DIR3[r.cand[a][1]];
+                    slot_offset(r.cand[a][0], o);
                     for (int j = 0; j < dim; ++j)
-                        if (dn[j] != 2 * o[j] + dq[j]) { ++bad; break; }              // same-level neighbour at offset o
+                        if (dir(r.node, j) != 2 * o[j] + dir(r.cand[a][1], j)) { ++bad; break; }   // same-level neighbour at offset o
                 }
             }
         }
