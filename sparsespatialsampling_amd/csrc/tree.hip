@@ -61,27 +61,30 @@ __device__ __forceinline__ bool inside(const BoxParams &g, const double (&x)[DIM
     return in;
 }
 
+// torch's norm over the last dimension of a [2^d, d] tensor sums the squares as one fused chain, fma(a2, a2, fma(a1, a1, a0*a0))
 template <int DIM>
 __device__ __forceinline__ bool inside(const SphereParams &g, const double (&x)[DIM]) {
     double s = 0.0;
 #pragma unroll
     for (int j = 0; j < DIM; ++j) {
         double t = x[j] - g.pos[j];
-        s += t * t;
+        s = j ? __fma_rn(t, t, s) : t * t;
     }
     return sqrt(s) <= g.radius;
 }
 
+// torch.cross rounds the second product of a component and fuses the first, fma(a, b, -(c*d)); the norm of the product is the
+// fused chain of the sphere; the projection is a plain sum
 template <int DIM>
 __device__ __forceinline__ bool inside(const CylParams &g, const double (&x)[DIM]) {
     static_assert(DIM == 3, "cylinder is 3-D only");
     double v[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) v[j] = x[j] - g.p0[j];
-    double c0 = g.axis[1] * v[2] - g.axis[2] * v[1];
-    double c1 = g.axis[2] * v[0] - g.axis[0] * v[2];
-    double c2 = g.axis[0] * v[1] - g.axis[1] * v[0];
-    double nd = sqrt(c0 * c0 + c1 * c1 + c2 * c2) / g.norm;
+    double c0 = __fma_rn(g.axis[1], v[2], -(g.axis[2] * v[1]));
+    double c1 = __fma_rn(g.axis[2], v[0], -(g.axis[0] * v[2]));
+    double c2 = __fma_rn(g.axis[0], v[1], -(g.axis[1] * v[0]));
+    double nd = sqrt(__fma_rn(c2, c2, __fma_rn(c1, c1, c0 * c0))) / g.norm;
     double proj = ((v[0] * g.axis[0] + v[1] * g.axis[1]) + v[2] * g.axis[2]) / g.norm;
     double rad = g.is_cone ? g.r0 + proj / g.norm * (g.r1 - g.r0) : g.r0;
     return (0.0 <= proj) & (proj <= g.norm) & (nd <= rad);

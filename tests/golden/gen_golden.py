@@ -13,6 +13,7 @@ Fixture groups:
     predict_*     KNeighborsRegressor(weights="distance").predict as used at s_cube.py:161-163,224,328,372
     masks         geometry check_cell truth tables                (geometry/*.py)
     masks_polytopes   the same for triangle / prism / tetrahedron / pyramid
+    masks_curved  sphere / cylinder / cone / box at exact and one-ulp ties: its own script, gen_masks_curved.py
     uniform_*     _refine_uniform() neighbour + node tables       (s_cube.py:508-561, 904-1536)
     refine_*      full SamplingTree.refine() outputs + traces     (s_cube.py:563-667)
     refine_random_<seed>   final grids of randomly drawn configurations (inputs.random_refine_case)

@@ -175,6 +175,61 @@ def polytope_cells(d, rng):
     return np.concatenate([c, cl]), np.concatenate([h, hl])
 
 
+# ---- ``masks_curved`` fixture: sphere / cylinder / cone / box on a mixed-level lattice ------------------------------------------
+# node directions of a cell in the reference's order (the one every mask generator and the oracle use)
+CELL_DIRS = {2: np.array([[-1, -1], [-1, 1], [1, 1], [1, -1]], dtype=np.float64),
+             3: np.array([[-1, -1, 1], [-1, 1, 1], [1, 1, 1], [1, -1, 1],
+                          [-1, -1, -1], [-1, 1, -1], [1, 1, -1], [1, -1, -1]], dtype=np.float64)}
+CURVED_LO, CURVED_WIDTH = -0.5, 2.0
+
+
+def curved_cells(d):
+    """all cells of levels 3 and 4 of the root cell [-0.5, 1.5]^d (64 + 256 in 2-D, 512 + 4096 in 3-D): centre and level per
+    cell, root width.  Every node lies on the 1/8 lattice."""
+    centers, levels = [], []
+    for lv in (3, 4):
+        n = 2 ** lv
+        x = CURVED_LO + (np.arange(n) + 0.5) * (CURVED_WIDTH / n)
+        c = np.stack(np.meshgrid(*[x] * d, indexing="ij"), -1).reshape(-1, d)
+        centers.append(c)
+        levels.append(np.full(len(c), lv, dtype=np.int32))
+    return np.ascontiguousarray(np.concatenate(centers)), np.concatenate(levels), CURVED_WIDTH
+
+
+def cell_nodes(center, level, width):
+    """[n, 2^d, d] nodes, centre + direction * (0.5 * width) / 2^level -- built as the ``masks`` generator builds them"""
+    h = (0.5 * width) / 2.0 ** level
+    return center[:, None, :] + CELL_DIRS[center.shape[1]][None] * h[:, None, None]
+
+
+# exact ties: dyadic bodies whose surface passes through lattice nodes (every operation of the predicate is exact).  Radii are
+# Pythagorean: 5/8 from (3,4,5); 3/8, 7/8, 9/8 from (1,2,2), (2,3,6), (1,4,8).  The cone's radius at the lattice plane z = k/8
+# is 1/2 - k/32.
+CURVED_EXACT = {
+    "sphere2": [([0.375, 0.5], 0.625), ([0.75, 0.25], 0.625)],
+    "sphere3": [([0.5, 0.5, 0.5], 0.375), ([0.5, 0.375, 0.625], 0.875), ([0.5, 0.5, 0.5], 1.125)],
+    "cyl": [([(0.5, 0.375, 0.0), (0.5, 0.375, 1.0)], 0.625), ([(0.125, 0.5, 0.5), (0.875, 0.5, 0.5)], 0.375)],
+    "cone": [([(0.5, 0.5, 0.0), (0.5, 0.5, 1.0)], [0.5, 0.25])],
+}
+# one-ulp ties: generic bodies; their radii (and, for the caps, end points) come from the reference's own arithmetic at chosen
+# nodes and are stored in the fixture
+CURVED_GENERIC = {
+    "sphere2": [0.37, 0.52],
+    "sphere3": [0.37, 0.52, 0.41],
+    "cyl": [(0.21, 0.33, -0.12), (0.87, 0.71, 0.93)],
+    "cone": [(0.15, 0.4, 0.05), (0.9, 0.65, 0.8)],
+    "cone_r1": 0.15,
+}
+_UP, _DOWN = float(np.nextafter(0.25, 1.0)), float(np.nextafter(1.0, 0.0))
+# boxes: bounds on lattice planes; bounds one ulp beside a lattice plane (the node on it is out on one side, in on the other) and
+# one bound that is a rounded sum
+CURVED_BOXES = {
+    2: [([0.25, 0.125], [1.0, 0.875]), ([_UP, float(np.nextafter(0.125, 0.0))], [_DOWN, 0.1 + 0.2])],
+    3: [([0.25, 0.125, 0.0], [1.0, 0.875, 0.75]),
+        ([_UP, float(np.nextafter(0.125, 0.0)), 0.1 + 0.2], [_DOWN, float(np.nextafter(0.875, 1.0)), 0.75])],
+}
+
+
 def c1_cylinder2d(geometry):
     """BASELINE config C1 realised synthetically: ~14 000 points in the cylinder2D channel, wake-like metric,
     Cube domain + Sphere body refined to level 9 (reference examples/s3_for_cylinder2D_Re100.py:43-52)"""
