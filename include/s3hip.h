@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 8
+#define S3_ABI_VERSION 9
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -310,6 +310,39 @@ int s3_interp_planned_src(s3_interp_plan *plan, const void *d_table, int dtype, 
 #define S3_ROUTE_CHUNK128      9   /* chunk kernel, 128-cell tiles */
 int s3_interp_plan_route(const s3_interp_plan *plan, int src, const void *d_data, int dtype, int64_t row_len, int64_t in_stride,
                          int32_t *h_out /*[5]*/);
+
+/* ---- reconstruction error: the exported fields back on the original CFD mesh (post_processing/compute_error_OAT.py:208-233) ----
+ * The reverse direction of a17: the table is the generated grid (nc cell centres, small, cache resident), the targets are the n
+ * points of the original mesh.  The reference fits KNeighborsRegressor(n_neighbors = 8 | 26, weights="distance") on the centres,
+ * predicts the whole field at the points ([n, T] f64 on the host) and reduces it to T + 1 + 2n numbers; here the prediction lives
+ * in registers only.
+ *
+ * s3_idw_weights_exact: scikit-learn's "distance" weights as the regressor applies them: a row with zero distances gets 1 at the
+ * zeros and 0 elsewhere, any other row 1/dist, and either way the row is normalised to sum 1.  NOT s3_idw_weights, whose
+ * 1/clamp(dist, 1e-12) belongs to export.py:428 (a point ON a cell centre gets 1e-10 of its neighbours there).
+ *
+ * s3_recon_error, one launch per snapshot batch.  Point i of the launch (i < n) is original row r = d_rows[i] (d_rows NULL: r = i,
+ * n_orig = n); d_w / d_idx / d_scale are in LAUNCH order (launch the points in the order of s3_spatial_order: neighbouring lanes
+ * then gather the same few grid rows), d_idx holds rows of d_grid (< nc, not checked on the device).  For every element l < row_len
+ *     fit = sum_{m<k} w[i,m] * grid[idx[i,m], l]      f64 fma chain over m = 0..k-1: the value does not depend on row_len
+ *     d   = s * (fit - orig[r, l]),   ref = s * orig[r, l]             s = d_scale[i], 1 without d_scale
+ * and the outputs are
+ *     d_mean[r], d_m2[r]   mean and centred second moment sum (|d| - mean)^2 of |d| over the row's row_len values (chunk mean first,
+ *                          then squared deviations, chunks merged with Chan's update: s3_row_moments' scheme, so that batches merge
+ *                          the same way); rows that are no point of the launch are not touched
+ *     d_colsum[2][row_len] sum_i d^2 and sum_i ref^2 per column: partial sums over blocks of S3_RECON_BLOCK consecutive points of the
+ *                          launch order, reduced by a second small kernel in a fixed order
+ * No floating-point atomics: the same inputs give the same bits on every run.  d_grid [nc][row_len] dense; d_orig rows with pitch
+ * orig_stride >= row_len elements (0 = row_len), any alignment; both f32 or f64 independently.  d_scratch:
+ * s3_recon_error_scratch_bytes(n, row_len) bytes. */
+#define S3_RECON_BLOCK 1024
+int s3_idw_weights_exact(const double *d_dist /*[n,k]*/, int64_t n, int k, double *d_w /*[n,k]*/, s3_stream stream);
+size_t s3_recon_error_scratch_bytes(int64_t n, int64_t row_len);
+int s3_recon_error(const double *d_w /*[n,k]*/, const int32_t *d_idx /*[n,k]*/, int64_t n, int k, const void *d_grid,
+                   int grid_dtype, int64_t nc, const void *d_orig, int orig_dtype, int64_t n_orig, int64_t orig_stride,
+                   int64_t row_len, const int32_t *d_rows /*[n] or NULL*/, const double *d_scale /*[n] or NULL*/,
+                   double *d_mean /*[n_orig]*/, double *d_m2 /*[n_orig]*/, double *d_colsum /*[2][row_len]*/, void *d_scratch,
+                   s3_stream stream);
 
 /* ---- yardsticks of the measurement (bench.py's roofline line; no counterpart in the reference, not on any product path) ----
  * s3_yard_stream      a hand-written streaming kernel over d_src: every lane reads `reads` 16-byte vectors (coalesced) and

@@ -19,3 +19,13 @@ if _os.environ.get("S3_KEEP_RUNTIME_PINNING") != "1":
     _os.environ.setdefault("GPU_PINNED_MIN_XFER_SIZE", "4096")
 
 from .version import __version__
+
+__all__ = ["ReconstructionError", "reconstruct", "__version__"]
+
+
+def __getattr__(name):
+    # (resolved on first use: importing the package alone loads neither torch nor the native library)
+    if name in ("ReconstructionError", "reconstruct"):
+        from . import reconstruction
+        return getattr(reconstruction, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -175,6 +175,70 @@ def interp(w, idx, data, out=None):
     return out
 
 
+def idw_weights_exact(dist):
+    """scikit-learn's ``weights="distance"`` as ``KNeighborsRegressor.predict`` applies them (s3_idw_weights_exact): a row with
+    zero distances gets 1 at the zeros and 0 elsewhere, any other row ``1 / dist``; rows normalised to sum 1.  Not
+    ``idw_weights``, whose clamp at 1e-12 is the export's rule."""
+    if not (dist.dtype == pt.float64 and dist.dim() == 2):
+        raise TypeError("idw_weights_exact: dist must be float64 [n, k]")
+    w = pt.empty_like(dist)
+    check(_lib.hip_lib().s3_idw_weights_exact(_ptr(dist), int(dist.shape[0]), int(dist.shape[1]), _ptr(w), _stream()),
+          "s3_idw_weights_exact")
+    return w
+
+
+RECON_BLOCK = 1024          # S3_RECON_BLOCK (s3hip.h): points per partial column sum
+
+
+def _pitched_rows(t, who):
+    """(row_len, stride in elements) of a device tensor whose leading axis is the row axis: contiguous [n, ...], or a 2-D column
+    slice ``buf[:, :L]`` of a wider buffer"""
+    if not t.is_cuda or t.dtype not in DTYPE_CODE or t.dim() < 1:
+        raise TypeError(f"{who}: float32 / float64 device tensor [n, ...] required")
+    row_len = int(np.prod(t.shape[1:])) if t.dim() > 1 else 1
+    if t.is_contiguous():
+        return row_len, row_len
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= row_len:
+        return row_len, int(t.stride(0))
+    raise TypeError(f"{who}: rows must be contiguous (a row pitch is allowed for a 2-D tensor)")
+
+
+def recon_error(w, idx, grid, orig, rows=None, scale=None, mean=None, m2=None):
+    """the fused reconstruction-error launch (s3_recon_error).  Point i of the launch is original row ``rows[i]`` (``rows`` None:
+    row i); ``w`` f64 / ``idx`` int32 [n, k] (rows of ``grid``) and ``scale`` f64 [n] are in launch order.  With
+    ``fit = sum_m w * grid[idx]``, ``d = scale * (fit - orig)`` and ``ref = scale * orig`` it returns
+    ``(mean, m2, colsum)``: mean and centred second moment of ``|d|`` over each original row (f64 [n_orig], original order;
+    written into ``mean`` / ``m2`` when given) and ``colsum`` f64 [2, row_len] = (sum_i d^2, sum_i ref^2) per column.
+    ``grid`` [nc, ...] contiguous, ``orig`` [n_orig, ...] contiguous or a pitched 2-D view; nothing of size n x row_len is
+    written."""
+    if not (w.dtype == pt.float64 and idx.dtype == pt.int32 and w.dim() == 2 and w.shape == idx.shape):
+        raise TypeError("recon_error: w must be float64 [n, k], idx int32 [n, k]")
+    n, k = int(w.shape[0]), int(w.shape[1])
+    row_len, g_stride = _pitched_rows(grid, "recon_error(grid)")
+    o_len, o_stride = _pitched_rows(orig, "recon_error(orig)")
+    if g_stride != row_len or o_len != row_len or row_len < 1:
+        raise TypeError("recon_error: grid must be contiguous and grid / orig rows of one length >= 1")
+    nc, n_orig = int(grid.shape[0]), int(orig.shape[0])
+    if rows is not None and not (rows.dtype == pt.int32 and rows.numel() == n):
+        raise TypeError("recon_error: rows must be int32 [n]")
+    if (rows is None and n_orig != n) or n_orig < n or nc < 1:
+        raise TypeError("recon_error: one original row per point required (or a row list)")
+    if scale is not None and not (scale.dtype == pt.float64 and scale.numel() == n):
+        raise TypeError("recon_error: scale must be float64 [n]")
+    dev = w.device
+    mean = pt.empty(n_orig, dtype=pt.float64, device=dev) if mean is None else mean
+    m2 = pt.empty(n_orig, dtype=pt.float64, device=dev) if m2 is None else m2
+    if not (mean.dtype == pt.float64 and m2.dtype == pt.float64 and mean.numel() == n_orig and m2.numel() == n_orig):
+        raise TypeError("recon_error: mean / m2 must be float64 [n_orig]")
+    colsum = pt.empty((2, row_len), dtype=pt.float64, device=dev)
+    lib = _lib.hip_lib()
+    scratch = pt.empty((lib.s3_recon_error_scratch_bytes(n, row_len) + 7) // 8, dtype=pt.float64, device=dev)
+    check(lib.s3_recon_error(_ptr(w), _ptr(idx), n, k, _ptr(grid), DTYPE_CODE[grid.dtype], nc, C.c_void_p(orig.data_ptr()),
+                             DTYPE_CODE[orig.dtype], n_orig, o_stride, row_len, _ptr(rows), _ptr(scale), _ptr(mean), _ptr(m2),
+                             _ptr(colsum), _ptr(scratch), _stream()), "s3_recon_error")
+    return mean, m2, colsum
+
+
 # ExportData queues its device-to-host copies on a stream of their own and lets them complete behind its back (the host-logic
 # tests replace this module by CPU stand-ins that do not have the attribute: there every copy is immediate)
 ASYNC_TRANSFERS = True
