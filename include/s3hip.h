@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 9
+#define S3_ABI_VERSION 10
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -442,6 +442,21 @@ int s3_weighted_gram(const double *d_x, int64_t n_rows, int64_t t, int64_t in_st
  * L [m][k] row pitch l_stride, B [k][n] contiguous, E [m][n] row pitch e_stride, C [m][n] contiguous; means may be NULL. */
 int s3_centered_gemm(const double *d_l, int64_t m, int64_t k, int64_t l_stride, const double *d_lmean, const double *d_b,
                      int64_t n, const double *d_e, int64_t e_stride, const double *d_emean, double *d_c, s3_stream stream);
+
+/* The same two kernels for a matrix read WHERE IT LIES, f32 or f64 (dtype: S3_DTYPE_*), behind the dynamic mode decomposition
+ * (post_processing/compare_dmd_OAT.py:150-178; sparsespatialsampling_amd/dmd.py): the original CFD field is f32 and 20 GB at the
+ * cylinder3D shape, a f64 copy of it is what these entry points avoid.  An f32 element is widened to f64 in the operand staging,
+ * before centring and weighting; the MFMA part and the slice-ordered reduction are the ones above, so
+ *   - s3_gram of an f32 matrix equals s3_gram of its f64 copy to the bit, and s3_tall_gemm likewise;
+ *   - s3_gram(f64, mean, weight) equals s3_weighted_gram, s3_tall_gemm(f64) equals s3_centered_gemm without means and d_e.
+ * s3_gram: d_mean NULL = no centring (DMD does not centre), d_weight NULL = 1.  s3_tall_gemm: C [m][n] = L [m][k] B [k][n], B and C
+ * f64 contiguous.  Rows may be pitched (in_stride / l_stride in ELEMENTS) and need the element's alignment only: f32 rows that
+ * are not all 16-byte aligned are read with 8- or 4-byte loads, chosen per launch from (pointer | stride * 4) & 15. */
+size_t s3_gram_scratch_bytes(int64_t n_rows, int64_t t);
+int s3_gram(const void *d_x, int dtype, int64_t n_rows, int64_t t, int64_t in_stride, const double *d_mean /*[n_rows] or NULL*/,
+            const double *d_weight /*[n_rows] or NULL*/, double *d_gram /*[t,t]*/, void *d_scratch, s3_stream stream);
+int s3_tall_gemm(const void *d_l, int dtype, int64_t m, int64_t k, int64_t l_stride, const double *d_b /*[k,n]*/, int64_t n,
+                 double *d_c /*[m,n]*/, s3_stream stream);
 
 /* Symmetric eigenproblem of the T x T Gram matrix (the step between s3_weighted_gram and the modes; the reference gets the whole
  * decomposition from flowtorch.analysis.SVD, utils.py:302-346).  The one LIBRARY call of the SVD path: rocSOLVER's dsyevd, looked up

@@ -20,7 +20,7 @@ if _os.environ.get("S3_KEEP_RUNTIME_PINNING") != "1":
 
 from .version import __version__
 
-__all__ = ["ReconstructionError", "reconstruct", "__version__"]
+__all__ = ["ReconstructionError", "reconstruct", "DMD", "__version__"]
 
 
 def __getattr__(name):
@@ -28,4 +28,7 @@ def __getattr__(name):
     if name in ("ReconstructionError", "reconstruct"):
         from . import reconstruction
         return getattr(reconstruction, name)
+    if name == "DMD":
+        from . import dmd
+        return dmd.DMD
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -12,9 +12,11 @@
 // Kernel: one 256-thread workgroup per (128 x 128 block of the upper triangle of G, slice of the rows).  Per step 16 rows
 // of the two column panels are loaded (coalesced 16-byte pieces), centred, weighted and stored to LDS; each wavefront
 // owns a 64 x 64 quarter = 4 x 4 MFMA tiles (128 accumulator VGPRs) and issues 16 MFMAs per 4 rows.  The row slices'
-// partial blocks are added in slice order by a second kernel (deterministic), which also mirrors the lower triangle.
+// partial blocks (cut to the part that lies inside G: a T of 130 keeps 128 x 128 + 128 x 2 + 2 x 2 values per slice, not three
+// 128 x 128 blocks) are added in slice order by a second kernel (deterministic), which also mirrors the lower triangle.
 #include "common.h"
 
+#include <algorithm>
 #include <vector>
 
 namespace s3 {
@@ -26,10 +28,49 @@ constexpr int GLD = GB + 16;       // LDS row pitch in doubles: consecutive rows
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
+// Operand staging by element type.  T = double is the matrix the interpolation kernel wrote (compute_svd); T = float is a field
+// read where it lies (the DMD of the original CFD field and of a float32 Dataloader: dmd.py) -- widened to f64 in registers,
+// BEFORE centring and weighting, so the staged value is the one the f64 staging makes of the matrix's .double() copy and the
+// two Gram matrices agree to the bit.  A 16-byte piece is PW = 2 doubles or 4 floats: 16 threads per row of a 16 x 128 panel take
+// 4 pieces at columns c0 + 32 p (double) or 2 pieces at c0 + 64 p (float), eight values per thread and panel either way.
+// VEC = elements per load instruction of a piece that lies inside the matrix: chosen per LAUNCH on the host from the alignment
+// every row start shares (stage_vec), never per lane; a piece across the matrix's edge is read element by element.
+// (T = double keeps the scalar form it always had: VEC = 1.)
+template <typename T> struct stage_traits;
+template <> struct stage_traits<double> { static constexpr int PW = 2; };
+template <> struct stage_traits<float> { static constexpr int PW = 4; };
+
+// out[j] = p[j] widened for j < avail, `fill` for the others (avail <= 0: nothing is read)
+template <typename T, int VEC, int PW>
+__device__ __forceinline__ void load_piece(const T *__restrict__ p, int avail, double fill, double (&out)[PW]) {
+    if constexpr (VEC > 1) {
+        if (avail >= PW) {
+            typedef T vec_t __attribute__((ext_vector_type(VEC)));
+#pragma unroll
+            for (int q = 0; q < PW; q += VEC) {
+                const vec_t v = *reinterpret_cast<const vec_t *>(p + q);
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) out[q + j] = (double)v[j];
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < PW; ++j) out[j] = j < avail ? (double)p[j] : fill;
+}
+
+// elements per load for float rows: every row start is (base + row * stride * 4) bytes, so the alignment all of them share is
+// the one of (base | stride * 4)
+static int stage_vec(const void *base, int64_t stride_elements) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(base) | (uintptr_t)(stride_elements * (int64_t)sizeof(float));
+    return (a & 15) == 0 ? 4 : (a & 7) == 0 ? 2 : 1;
+}
+
+template <typename T, int VEC>
 __global__ void __launch_bounds__(256)
-gram_block_kernel(const double *__restrict__ x, int64_t n_rows, int t, int64_t in_stride, const double *__restrict__ mean,
-                  const double *__restrict__ weight, const int2 *__restrict__ pairs, int64_t rows_per_slice,
-                  double *__restrict__ partial /*[slice][pair][GB][GB]*/) {
+gram_block_kernel(const T *__restrict__ x, int64_t n_rows, int t, int64_t in_stride, const double *__restrict__ mean,
+                  const double *__restrict__ weight, const int2 *__restrict__ pairs,
+                  const int64_t *__restrict__ offs, int64_t rows_per_slice, double *__restrict__ partial /*[slice][offs[pair] ...]*/) {
     __shared__ double sA[2][GK][GLD];
     __shared__ double sB[2][GK][GLD];
     const int pair = blockIdx.x, slice = blockIdx.y;
@@ -45,37 +86,33 @@ gram_block_kernel(const double *__restrict__ x, int64_t n_rows, int t, int64_t i
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = double4_t{0.0, 0.0, 0.0, 0.0};
 
-    // staging role: 16 threads per row, each 4 pieces of 2 doubles per panel (columns c2, c2 + 32, c2 + 64, c2 + 96).  The
-    // raw loads of step s + 1 are issued before the MFMAs of step s and land in registers; they are centred, weighted
+    // staging role: 16 threads per row, each NP pieces of PW columns per panel (columns c0 + PSTEP p: stage_traits).  The
+    // raw loads of step s + 1 are issued before the MFMAs of step s and land in registers (widened); they are centred, weighted
     // and written to the other LDS buffer after the MFMAs (global latency hidden behind ~4000 cycles of matrix work)
-    const int srow = threadIdx.x >> 4, c2 = (threadIdx.x & 15) * 2;
-    double ra[4][2], rb[4][2], mu = 0.0, sw = 0.0;
+    constexpr int PW = stage_traits<T>::PW, NP = 8 / PW, PSTEP = 16 * PW;
+    const int srow = threadIdx.x >> 4, c0 = (threadIdx.x & 15) * PW;
+    double ra[NP][PW], rb[NP][PW], mu = 0.0, sw = 0.0;
     auto load = [&](int64_t row_base) {
         const int64_t row = row_base + srow;
         const bool ok = row < r1;
-        mu = ok ? mean[row] : 0.0;
-        sw = ok ? sqrt(weight[row]) : 0.0;                        // sw = 0 zeroes the padding rows
-        const double *xr = x + (ok ? row : 0) * in_stride;
+        mu = ok && mean ? mean[row] : 0.0;                        // (no mean: x - 0 is x; no weight: x * 1 is x)
+        sw = ok ? (weight ? sqrt(weight[row]) : 1.0) : 0.0;       // sw = 0 zeroes the padding rows
+        const T *xr = x + (ok ? row : 0) * in_stride;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int ca = bi * GB + c2 + 32 * p, cb = bj * GB + c2 + 32 * p;
-            ra[p][0] = ca < t ? xr[ca] : mu;                      // columns past t contribute (mu - mu) * sw = 0
-            ra[p][1] = ca + 1 < t ? xr[ca + 1] : mu;
-            if (!diagonal) {
-                rb[p][0] = cb < t ? xr[cb] : mu;
-                rb[p][1] = cb + 1 < t ? xr[cb + 1] : mu;
-            }
+        for (int p = 0; p < NP; ++p) {
+            const int ca = bi * GB + c0 + PSTEP * p, cb = bj * GB + c0 + PSTEP * p;
+            load_piece<T, VEC, PW>(xr + ca, t - ca, mu, ra[p]);   // columns past t contribute (mu - mu) * sw = 0
+            if (!diagonal) load_piece<T, VEC, PW>(xr + cb, t - cb, mu, rb[p]);
         }
     };
     auto store = [&](int buf) {
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int c = c2 + 32 * p;
-            sA[buf][srow][c] = (ra[p][0] - mu) * sw;
-            sA[buf][srow][c + 1] = (ra[p][1] - mu) * sw;
-            if (!diagonal) {
-                sB[buf][srow][c] = (rb[p][0] - mu) * sw;
-                sB[buf][srow][c + 1] = (rb[p][1] - mu) * sw;
+        for (int p = 0; p < NP; ++p) {
+            const int c = c0 + PSTEP * p;
+#pragma unroll
+            for (int j = 0; j < PW; ++j) {
+                sA[buf][srow][c + j] = (ra[p][j] - mu) * sw;
+                if (!diagonal) sB[buf][srow][c + j] = (rb[p][j] - mu) * sw;
             }
         }
     };
@@ -110,8 +147,10 @@ gram_block_kernel(const double *__restrict__ x, int64_t n_rows, int t, int64_t i
         buf ^= 1;
     }
 
-    // C/D layout of v_mfma_f64_16x16x4_f64: column = lane & 15, row = (lane >> 4) + 4 * register
-    double *out = partial + ((int64_t)slice * gridDim.x + pair) * GB * GB;
+    // C/D layout of v_mfma_f64_16x16x4_f64: column = lane & 15, row = (lane >> 4) + 4 * register.  Only the part of the block inside
+    // G is kept: [rows][cols] dense at offs[pair] of the slice's record (offs[n_pairs] doubles per slice)
+    const int rows = min(GB, t - bi * GB), cols = min(GB, t - bj * GB);
+    double *out = partial + (int64_t)slice * offs[gridDim.x] + offs[pair];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -119,40 +158,43 @@ gram_block_kernel(const double *__restrict__ x, int64_t n_rows, int t, int64_t i
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int gr = wi * 64 + i * 16 + (lane >> 4) + 4 * r, gc = wj * 64 + j * 16 + (lane & 15);
-                out[gr * GB + gc] = acc[i][j][r];
+                if (gr < rows && gc < cols) out[gr * cols + gc] = acc[i][j][r];
             }
 }
 
 // G block = sum over the row slices in slice order; upper block written as is, lower block mirrored
 __global__ void __launch_bounds__(256)
-gram_reduce_kernel(const double *__restrict__ partial, const int2 *__restrict__ pairs, int n_pairs, int n_slices, int t,
-                   double *__restrict__ g) {
+gram_reduce_kernel(const double *__restrict__ partial, const int2 *__restrict__ pairs, const int64_t *__restrict__ offs, int n_pairs,
+                   int n_slices, int t, double *__restrict__ g) {
     const int pair = blockIdx.x;
     const int bi = pairs[pair].x, bj = pairs[pair].y;
-    {
-        const int e = blockIdx.y * 256 + threadIdx.x;            // one entry of the block per lane
+    const int rows = min(GB, t - bi * GB), cols = min(GB, t - bj * GB);
+    const int e = blockIdx.y * 256 + threadIdx.x;                // one entry of the block per lane
+    const int br = e / GB, bc = e % GB;
+    if (br < rows && bc < cols) {
+        const double *src = partial + offs[pair] + br * cols + bc;
+        const int64_t per_slice = offs[n_pairs];
         double s = 0.0;
-        for (int sl = 0; sl < n_slices; ++sl) s += partial[((int64_t)sl * n_pairs + pair) * GB * GB + e];
-        const int r = bi * GB + e / GB, c = bj * GB + e % GB;
-        if (r < t && c < t) {
-            if (bi != bj || c >= r) g[(int64_t)r * t + c] = s;
-            if (bi != bj || c > r) g[(int64_t)c * t + r] = s;
-        }
+        for (int sl = 0; sl < n_slices; ++sl) s += src[(int64_t)sl * per_slice];
+        const int r = bi * GB + br, c = bj * GB + bc;
+        if (bi != bj || c >= r) g[(int64_t)r * t + c] = s;
+        if (bi != bj || c > r) g[(int64_t)c * t + r] = s;
     }
 }
 
 // C = (L - lmean 1^T) B                       (E == nullptr)      the modes U = (X - mean) V S^-1 and the coefficients (X - mean) V
 // C = (E - emean 1^T) - (L - lmean 1^T) B     (E != nullptr)      the residual (X - mean) - A V^T of a deflation level
-// L [m][k] (row pitch l_stride), B [k][n] contiguous, E [m][n] (row pitch e_stride), C [m][n] contiguous, all f64
+// L [m][k] (row pitch l_stride; T = double, or float widened in the staging: s3_tall_gemm), B [k][n] contiguous, E [m][n] (row
+// pitch e_stride), C [m][n] contiguous, all f64
 // (reference utils.py:302-346 gets U from the SVD itself; here the tall matrix never leaves HBM).  One 256-thread workgroup per
 // 128 x 128 block of C; per step 16 columns of L and 16 rows of B go through LDS -- the L tile transposed on the way so that
 // both MFMA operands are read like the Gram kernel reads its panels (sA[k][row], sB[k][column]) -- each wavefront owns a
 // 64 x 64 quarter = 4 x 4 tiles of v_mfma_f64_16x16x4_f64; the raw loads of step s + 1 are issued before the MFMAs of step s.
 // NJ = 16-column tiles per wavefront and row of tiles: 4 -> a 128 x 128 block of C, 2 -> 128 x 64 (right-hand sides of up to 64
 // columns -- compute_svd(rank=50) -- would issue 128 columns' worth of MFMAs for 50 otherwise)
-template <int NJ>
+template <typename T, int VEC, int NJ>
 __global__ void __launch_bounds__(256, 2)      // 198 VGPRs at NJ = 4; without the second bound the compiler takes 316 = one wavefront per SIMD: 31 instead of 44 TFLOP/s
-centered_gemm_kernel(const double *__restrict__ l, int64_t m, int k, int64_t l_stride, const double *__restrict__ lmean,
+centered_gemm_kernel(const T *__restrict__ l, int64_t m, int k, int64_t l_stride, const double *__restrict__ lmean,
                      const double *__restrict__ b, int n, const double *__restrict__ e, int64_t e_stride,
                      const double *__restrict__ emean, double *__restrict__ c) {
     constexpr int BN = 32 * NJ;                      // columns of C per workgroup
@@ -175,14 +217,25 @@ centered_gemm_kernel(const double *__restrict__ l, int64_t m, int k, int64_t l_s
     const int64_t row_l = m0 + lrow;
     const bool row_ok = row_l < m;
     const double mu = row_ok && lmean ? lmean[row_l] : 0.0;
-    const double *lr = l + (row_ok ? row_l : 0) * l_stride;
+    const T *lr = l + (row_ok ? row_l : 0) * l_stride;
     const int brow = threadIdx.x >> 4, c2 = (threadIdx.x & 15) * 2;
     double ra[8], rb[NJ][2];
     auto load = [&](int k0) {
+        if constexpr (sizeof(T) == 8) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int kk = k0 + lk + i;
-            ra[i] = row_ok && kk < k ? lr[kk] - mu : 0.0;          // rows / columns past the matrix contribute nothing
+            for (int i = 0; i < 8; ++i) {
+                const int kk = k0 + lk + i;
+                ra[i] = row_ok && kk < k ? lr[kk] - mu : 0.0;      // rows / columns past the matrix contribute nothing
+            }
+        } else {                                                   // float: two 16-byte pieces of four columns, widened, then centred
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int kk = k0 + lk + 4 * h;
+                double piece[4];
+                load_piece<T, VEC, 4>(lr + kk, row_ok ? k - kk : 0, mu, piece);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ra[4 * h + j] = piece[j] - mu;   // (mu - mu = 0 past the matrix)
+            }
         }
         const int kb = k0 + brow;
         const double *br = b + (int64_t)(kb < k ? kb : 0) * n;
@@ -248,6 +301,115 @@ centered_gemm_kernel(const double *__restrict__ l, int64_t m, int k, int64_t l_s
         }
 }
 
+// ---- host side, shared by the f64 entry points of compute_svd and the typed ones of the DMD ----
+
+template <typename T, int VEC>
+static void launch_gemm(const T *d_l, int64_t m, int k, int64_t l_stride, const double *d_lmean, const double *d_b, int n, const double *d_e,
+                        int64_t e_stride, const double *d_emean, double *d_c, hipStream_t st) {
+    const bool narrow = n <= 64;                     // (one 64-column block: half the MFMAs of a 128-column one)
+    const int64_t bn = narrow ? 64 : GB;
+    const dim3 grid((unsigned)((m + GB - 1) / GB), (unsigned)((n + bn - 1) / bn));
+    if (narrow)
+        centered_gemm_kernel<T, VEC, 2><<<grid, 256, 0, st>>>(d_l, m, k, l_stride, d_lmean, d_b, n, d_e, e_stride, d_emean, d_c);
+    else
+        centered_gemm_kernel<T, VEC, 4><<<grid, 256, 0, st>>>(d_l, m, k, l_stride, d_lmean, d_b, n, d_e, e_stride, d_emean, d_c);
+}
+
+static int gemm_run(const char *who, const void *d_l, int dtype, int64_t m, int64_t k, int64_t l_stride, const double *d_lmean,
+                    const double *d_b, int64_t n, const double *d_e, int64_t e_stride, const double *d_emean, double *d_c, s3_stream stream) {
+    S3_REQUIRE(d_l && d_b && d_c, "%s: null array", who);
+    S3_REQUIRE(dtype == S3_DTYPE_F32 || dtype == S3_DTYPE_F64, "%s: dtype %d is neither f32 nor f64", who, dtype);
+    S3_REQUIRE(m >= 1 && k >= 1 && n >= 1 && k < (1 << 24) && n < (1 << 24) && l_stride >= k && (d_e == nullptr || e_stride >= n),
+               "%s: bad sizes (m %lld, k %lld, n %lld)", who, (long long)m, (long long)k, (long long)n);
+    const int64_t gx = (m + GB - 1) / GB, gy = (n + (n <= 64 ? 64 : GB) - 1) / (n <= 64 ? 64 : GB);
+    S3_REQUIRE(gx < ((int64_t)1 << 31) && gy <= 65535, "%s: shape too large for one launch", who);
+    hipStream_t st = as_stream(stream);
+    if (dtype == S3_DTYPE_F64) {
+        launch_gemm<double, 1>(static_cast<const double *>(d_l), m, (int)k, l_stride, d_lmean, d_b, (int)n, d_e, e_stride, d_emean, d_c, st);
+    } else {
+        const float *lf = static_cast<const float *>(d_l);
+        switch (stage_vec(d_l, l_stride)) {
+        case 4: launch_gemm<float, 4>(lf, m, (int)k, l_stride, d_lmean, d_b, (int)n, d_e, e_stride, d_emean, d_c, st); break;
+        case 2: launch_gemm<float, 2>(lf, m, (int)k, l_stride, d_lmean, d_b, (int)n, d_e, e_stride, d_emean, d_c, st); break;
+        default: launch_gemm<float, 1>(lf, m, (int)k, l_stride, d_lmean, d_b, (int)n, d_e, e_stride, d_emean, d_c, st); break;
+        }
+    }
+    S3_LAUNCH_CHECK();
+    return S3_OK;
+}
+
+// row slices of the Gram kernel: enough workgroups to fill the chip, at least 16 steps of GK rows per slice
+static int64_t gram_slices(int64_t n_rows, int64_t n_pairs) {
+    int64_t slices = (1024 + n_pairs - 1) / n_pairs;
+    const int64_t max_slices = (n_rows + 16 * GK - 1) / (16 * GK);
+    if (slices > max_slices) slices = max_slices;
+    return slices < 1 ? 1 : slices;
+}
+
+// doubles of one slice's record: the blocks (i, j >= i) of the upper triangle, each cut to the part inside G
+static int64_t gram_record(int64_t t) {
+    const int64_t nb = (t + GB - 1) / GB, last = t - (nb - 1) * GB;          // nb - 1 full block rows / columns and one of `last`
+    const int64_t full = nb - 1;
+    return full * (full + 1) / 2 * GB * GB + full * GB * last + last * last;
+}
+
+// scratch: [slices][record] doubles, [n_pairs] int2 block coordinates, [n_pairs + 1] int64 offsets into a record
+static size_t gram_scratch_bytes(int64_t n_rows, int64_t t) {
+    if (n_rows < 1 || t < 1) return 0;
+    const int64_t nb = (t + GB - 1) / GB, n_pairs = nb * (nb + 1) / 2;
+    return (size_t)(gram_slices(n_rows, n_pairs) * gram_record(t)) * sizeof(double) + (size_t)n_pairs * sizeof(int2) +
+           (size_t)(n_pairs + 1) * sizeof(int64_t) + 64;
+}
+
+static int gram_run(const char *who, const void *d_x, int dtype, int64_t n_rows, int64_t t, int64_t in_stride, const double *d_mean,
+                    const double *d_weight, double *d_gram, void *d_scratch, s3_stream stream) {
+    S3_REQUIRE(d_x && d_gram && d_scratch, "%s: null array", who);
+    S3_REQUIRE(dtype == S3_DTYPE_F32 || dtype == S3_DTYPE_F64, "%s: dtype %d is neither f32 nor f64", who, dtype);
+    S3_REQUIRE(n_rows >= 1 && t >= 1 && t < (1 << 20) && in_stride >= t, "%s: bad sizes (rows %lld, t %lld, stride %lld)", who,
+               (long long)n_rows, (long long)t, (long long)in_stride);
+    hipStream_t st = as_stream(stream);
+    const int nb = (int)((t + GB - 1) / GB), n_pairs = nb * (nb + 1) / 2;
+    int64_t slices = gram_slices(n_rows, n_pairs);
+    int64_t rows_per_slice = (n_rows + slices - 1) / slices;
+    rows_per_slice = (rows_per_slice + GK - 1) / GK * GK;
+    slices = (n_rows + rows_per_slice - 1) / rows_per_slice;
+    S3_REQUIRE(slices < 65536, "%s: too many row slices", who);
+    double *d_partial = static_cast<double *>(d_scratch);
+    const int64_t record = gram_record(t);
+    int2 *d_pairs = reinterpret_cast<int2 *>(d_partial + (size_t)slices * record);
+    int64_t *d_offs = reinterpret_cast<int64_t *>(d_pairs + n_pairs);
+    std::vector<int2> pairs;
+    std::vector<int64_t> offs;
+    int64_t off = 0;
+    for (int i = 0; i < nb; ++i)
+        for (int j = i; j < nb; ++j) {
+            pairs.push_back(make_int2(i, j));
+            offs.push_back(off);
+            off += std::min<int64_t>(GB, t - (int64_t)i * GB) * std::min<int64_t>(GB, t - (int64_t)j * GB);
+        }
+    offs.push_back(off);
+    S3_REQUIRE(off == record, "%s: internal: record size", who);
+    S3_HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(int2) * pairs.size(), hipMemcpyHostToDevice, st));
+    S3_HIP_CHECK(hipMemcpyAsync(d_offs, offs.data(), sizeof(int64_t) * offs.size(), hipMemcpyHostToDevice, st));
+    S3_HIP_CHECK(hipStreamSynchronize(st));               // `pairs` and `offs` are locals
+    const dim3 grid((unsigned)n_pairs, (unsigned)slices);
+    if (dtype == S3_DTYPE_F64) {
+        gram_block_kernel<double, 1><<<grid, 256, 0, st>>>(static_cast<const double *>(d_x), n_rows, (int)t, in_stride, d_mean, d_weight, d_pairs,
+                                                          d_offs, rows_per_slice, d_partial);
+    } else {
+        const float *xf = static_cast<const float *>(d_x);
+        switch (stage_vec(d_x, in_stride)) {
+        case 4: gram_block_kernel<float, 4><<<grid, 256, 0, st>>>(xf, n_rows, (int)t, in_stride, d_mean, d_weight, d_pairs, d_offs, rows_per_slice, d_partial); break;
+        case 2: gram_block_kernel<float, 2><<<grid, 256, 0, st>>>(xf, n_rows, (int)t, in_stride, d_mean, d_weight, d_pairs, d_offs, rows_per_slice, d_partial); break;
+        default: gram_block_kernel<float, 1><<<grid, 256, 0, st>>>(xf, n_rows, (int)t, in_stride, d_mean, d_weight, d_pairs, d_offs, rows_per_slice, d_partial); break;
+        }
+    }
+    S3_LAUNCH_CHECK();
+    gram_reduce_kernel<<<dim3((unsigned)n_pairs, GB * GB / 256), 256, 0, st>>>(d_partial, d_pairs, d_offs, n_pairs, (int)slices, (int)t, d_gram);
+    S3_LAUNCH_CHECK();
+    return S3_OK;
+}
+
 }  // namespace s3
 
 using namespace s3;
@@ -256,61 +418,27 @@ extern "C" {
 
 int s3_centered_gemm(const double *d_l, int64_t m, int64_t k, int64_t l_stride, const double *d_lmean, const double *d_b,
                      int64_t n, const double *d_e, int64_t e_stride, const double *d_emean, double *d_c, s3_stream stream) {
-    S3_REQUIRE(d_l && d_b && d_c, "s3_centered_gemm: null array");
-    S3_REQUIRE(m >= 1 && k >= 1 && n >= 1 && k < (1 << 24) && n < (1 << 24) && l_stride >= k && (d_e == nullptr || e_stride >= n),
-               "s3_centered_gemm: bad sizes (m %lld, k %lld, n %lld)", (long long)m, (long long)k, (long long)n);
-    const bool narrow = n <= 64;                     // (one 64-column block: half the MFMAs of a 128-column one)
-    const int64_t bn = narrow ? 64 : GB;
-    const int64_t gx = (m + GB - 1) / GB, gy = (n + bn - 1) / bn;
-    S3_REQUIRE(gx < ((int64_t)1 << 31) && gy <= 65535, "s3_centered_gemm: shape too large for one launch");
-    if (narrow)
-        centered_gemm_kernel<2><<<dim3((unsigned)gx, (unsigned)gy), 256, 0, as_stream(stream)>>>(d_l, m, (int)k, l_stride, d_lmean, d_b,
-                                                                                                (int)n, d_e, e_stride, d_emean, d_c);
-    else
-        centered_gemm_kernel<4><<<dim3((unsigned)gx, (unsigned)gy), 256, 0, as_stream(stream)>>>(d_l, m, (int)k, l_stride, d_lmean, d_b,
-                                                                                                (int)n, d_e, e_stride, d_emean, d_c);
-    S3_LAUNCH_CHECK();
-    return S3_OK;
+    return gemm_run("s3_centered_gemm", d_l, S3_DTYPE_F64, m, k, l_stride, d_lmean, d_b, n, d_e, e_stride, d_emean, d_c, stream);
 }
 
-size_t s3_weighted_gram_scratch_bytes(int64_t n_rows, int64_t t) {
-    if (n_rows < 1 || t < 1) return 0;
-    const int64_t nb = (t + GB - 1) / GB, n_pairs = nb * (nb + 1) / 2;
-    int64_t slices = (1024 + n_pairs - 1) / n_pairs;
-    const int64_t max_slices = (n_rows + 16 * GK - 1) / (16 * GK);
-    if (slices > max_slices) slices = max_slices;
-    if (slices < 1) slices = 1;
-    return (size_t)(slices * n_pairs) * GB * GB * sizeof(double) + (size_t)n_pairs * sizeof(int2) + 64;
+int s3_tall_gemm(const void *d_l, int dtype, int64_t m, int64_t k, int64_t l_stride, const double *d_b, int64_t n, double *d_c,
+                 s3_stream stream) {
+    return gemm_run("s3_tall_gemm", d_l, dtype, m, k, l_stride, nullptr, d_b, n, nullptr, 0, nullptr, d_c, stream);
 }
+
+size_t s3_weighted_gram_scratch_bytes(int64_t n_rows, int64_t t) { return gram_scratch_bytes(n_rows, t); }
+
+size_t s3_gram_scratch_bytes(int64_t n_rows, int64_t t) { return gram_scratch_bytes(n_rows, t); }
 
 int s3_weighted_gram(const double *d_x, int64_t n_rows, int64_t t, int64_t in_stride, const double *d_mean,
                      const double *d_weight, double *d_gram, void *d_scratch, s3_stream stream) {
-    S3_REQUIRE(d_x && d_mean && d_weight && d_gram && d_scratch, "s3_weighted_gram: null array");
-    S3_REQUIRE(n_rows >= 1 && t >= 1 && t < (1 << 20) && in_stride >= t, "s3_weighted_gram: bad sizes (rows %lld, t %lld, stride %lld)",
-               (long long)n_rows, (long long)t, (long long)in_stride);
-    hipStream_t st = as_stream(stream);
-    const int nb = (int)((t + GB - 1) / GB), n_pairs = nb * (nb + 1) / 2;
-    int64_t slices = (1024 + n_pairs - 1) / n_pairs;
-    const int64_t max_slices = (n_rows + 16 * GK - 1) / (16 * GK);
-    if (slices > max_slices) slices = max_slices;
-    if (slices < 1) slices = 1;
-    int64_t rows_per_slice = (n_rows + slices - 1) / slices;
-    rows_per_slice = (rows_per_slice + GK - 1) / GK * GK;
-    slices = (n_rows + rows_per_slice - 1) / rows_per_slice;
-    S3_REQUIRE(slices < 65536, "s3_weighted_gram: too many row slices");
-    double *d_partial = static_cast<double *>(d_scratch);
-    int2 *d_pairs = reinterpret_cast<int2 *>(d_partial + (size_t)slices * n_pairs * GB * GB);
-    std::vector<int2> pairs;
-    for (int i = 0; i < nb; ++i)
-        for (int j = i; j < nb; ++j) pairs.push_back(make_int2(i, j));
-    S3_HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(int2) * pairs.size(), hipMemcpyHostToDevice, st));
-    S3_HIP_CHECK(hipStreamSynchronize(st));               // `pairs` is a local
-    gram_block_kernel<<<dim3((unsigned)n_pairs, (unsigned)slices), 256, 0, st>>>(d_x, n_rows, (int)t, in_stride, d_mean, d_weight,
-                                                                                d_pairs, rows_per_slice, d_partial);
-    S3_LAUNCH_CHECK();
-    gram_reduce_kernel<<<dim3((unsigned)n_pairs, GB * GB / 256), 256, 0, st>>>(d_partial, d_pairs, n_pairs, (int)slices, (int)t, d_gram);
-    S3_LAUNCH_CHECK();
-    return S3_OK;
+    S3_REQUIRE(d_mean && d_weight, "s3_weighted_gram: null array");
+    return gram_run("s3_weighted_gram", d_x, S3_DTYPE_F64, n_rows, t, in_stride, d_mean, d_weight, d_gram, d_scratch, stream);
+}
+
+int s3_gram(const void *d_x, int dtype, int64_t n_rows, int64_t t, int64_t in_stride, const double *d_mean, const double *d_weight,
+            double *d_gram, void *d_scratch, s3_stream stream) {
+    return gram_run("s3_gram", d_x, dtype, n_rows, t, in_stride, d_mean, d_weight, d_gram, d_scratch, stream);
 }
 
 }  // extern "C"

@@ -239,6 +239,56 @@ def recon_error(w, idx, grid, orig, rows=None, scale=None, mean=None, m2=None):
     return mean, m2, colsum
 
 
+def _pitched_matrix(t, who):
+    """row pitch in elements of a 2-D f32 / f64 device matrix with unit inner stride, read where it lies"""
+    if not (t.is_cuda and t.dtype in DTYPE_CODE and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
+        raise TypeError(f"{who}: 2-D float32 / float64 device matrix with unit inner stride required")
+    return int(t.stride(0))
+
+
+def gram(x, mean=None, weight=None, out=None, scratch=None):
+    """``sum_n weight[n] (x[n] - mean[n]) (x[n] - mean[n])^T`` -> f64 [T, T] on the f64 matrix cores (s3_gram).  ``x`` [N, T] float32 or
+    float64 on the device, rows may be pitched; it is read where it lies, float32 is widened in the kernel's staging (the result
+    equals the one of ``x.double()`` to the bit).  ``mean`` / ``weight`` f64 device vectors [N] or None (no centring / weight 1)."""
+    stride = _pitched_matrix(x, "gram")
+    n, t = int(x.shape[0]), int(x.shape[1])
+    if n < 1 or t < 1:
+        raise ValueError(f"gram: empty matrix {tuple(x.shape)}")
+    for name, v in (("mean", mean), ("weight", weight)):
+        if v is not None and not (v.is_cuda and v.dtype == pt.float64 and v.numel() == n):
+            raise TypeError(f"gram: {name} must be a float64 device vector [{n}]")
+    lib = _lib.hip_lib()
+    need = int(lib.s3_gram_scratch_bytes(n, t))
+    if scratch is None:
+        scratch = pt.empty((need + 7) // 8, dtype=pt.float64, device=x.device)
+    elif scratch.numel() * scratch.element_size() < need:
+        raise ValueError("gram: scratch too small")
+    out = pt.empty((t, t), dtype=pt.float64, device=x.device) if out is None else out
+    if not (out.dtype == pt.float64 and tuple(out.shape) == (t, t)):
+        raise TypeError("gram: out must be float64 [T, T]")
+    check(lib.s3_gram(C.c_void_p(x.data_ptr()), DTYPE_CODE[x.dtype], n, t, stride, _ptr(mean), _ptr(weight), _ptr(out), _ptr(scratch),
+                      _stream()), "s3_gram")
+    return out
+
+
+def tall_gemm(left, b, out=None):
+    """``left @ b`` -> f64 [m, n] on the f64 matrix cores (s3_tall_gemm).  ``left`` [m, k] float32 or float64 on the device, rows may be
+    pitched, read where it lies; ``b`` [k, n] f64 contiguous on the device."""
+    stride = _pitched_matrix(left, "tall_gemm")
+    m, k = int(left.shape[0]), int(left.shape[1])
+    if not (b.is_cuda and b.dtype == pt.float64 and b.dim() == 2 and b.is_contiguous() and int(b.shape[0]) == k):
+        raise TypeError(f"tall_gemm: b must be a contiguous float64 device matrix [{k}, n]")
+    n = int(b.shape[1])
+    if m < 1 or k < 1 or n < 1:
+        raise ValueError(f"tall_gemm: empty product [{m}, {k}] x [{k}, {n}]")
+    out = pt.empty((m, n), dtype=pt.float64, device=left.device) if out is None else out
+    if not (out.dtype == pt.float64 and tuple(out.shape) == (m, n)):
+        raise TypeError("tall_gemm: out must be float64 [m, n]")
+    check(_lib.hip_lib().s3_tall_gemm(C.c_void_p(left.data_ptr()), DTYPE_CODE[left.dtype], m, k, stride, _ptr(b), n, _ptr(out), _stream()),
+          "s3_tall_gemm")
+    return out
+
+
 # ExportData queues its device-to-host copies on a stream of their own and lets them complete behind its back (the host-logic
 # tests replace this module by CPU stand-ins that do not have the attribute: there every copy is immediate)
 ASYNC_TRANSFERS = True

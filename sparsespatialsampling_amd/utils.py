@@ -13,6 +13,7 @@ import logging
 from typing import Callable, Union
 
 from .svd import compute_svd, write_svd_s_cube_to_file  # noqa: F401  (re-exported under the reference's names)
+from .dmd import DMD  # noqa: F401  (the reference's scripts take it from flowtorch.analysis: post_processing/compare_dmd_OAT.py)
 
 logger = logging.getLogger(__name__)
 
