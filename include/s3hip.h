@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 10
+#define S3_ABI_VERSION 11
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -234,6 +234,23 @@ int s3_snapshot_major(const double *d_in, int64_t nc, int n_comp, int64_t n_snap
  * s3_host_register: the values cross this rank's own PCIe link, nothing is sent to the rank that writes the file). */
 int s3_snapshot_major_rows(const double *d_in, int64_t nc, int n_comp, int64_t n_snapshots, const int32_t *d_rows /*[nc]*/,
                            int64_t n_out, double *d_out, s3_stream stream);
+/* Both with the STORAGE TYPE of the file as an argument (out_dtype: S3_DTYPE_*; this build's addition, the reference always
+ * stores float64 at export.py:283-299).  S3_DTYPE_F64: the bytes of the two entry points above.  S3_DTYPE_F32: every value is
+ * rounded ONCE, to nearest even, after the float64 accumulation -- by integer arithmetic on the bit pattern, so the result is
+ * the host's cast (numpy astype(float32)) whatever the kernel's denormal mode: ties, results that are f32 subnormals, +-0 for
+ * magnitudes below 2^-150 (sign kept), +-inf from FLT_MAX + 2^103 on.  d_out then holds floats (4-byte aligned; the store
+ * width follows the alignment of d_out and of the row length n_out * n_comp), download, staging and file bytes halve. */
+int s3_snapshot_major_as(const double *d_in, int64_t nc, int n_comp, int64_t n_snapshots, int out_dtype, void *d_out,
+                         s3_stream stream);
+int s3_snapshot_major_rows_as(const double *d_in, int64_t nc, int n_comp, int64_t n_snapshots, const int32_t *d_rows /*[nc]*/,
+                              int64_t n_out, int out_dtype, void *d_out, s3_stream stream);
+/* The loader's inverse (reference data.py:249-300 reads one dataset per write time and stacks them on the host): n_snapshots
+ * datasets [nc][n_comp] of in_dtype, back to back as the file holds them, become columns [t0, t0 + n_snapshots) of the
+ * cell-major matrix d_out [nc][n_comp][n_cols] of out_dtype (row pitch out_stride >= n_cols elements) that SVD and DMD read.
+ * f64 -> f32 rounds as above, f32 -> f64 is exact, equal types copy the bits.  Columns outside the range and the padding
+ * of the rows are not written. */
+int s3_cell_major(const void *d_in, int in_dtype, int64_t n_snapshots, int64_t nc, int n_comp, void *d_out, int out_dtype,
+                  int64_t n_cols, int64_t out_stride, int64_t t0, s3_stream stream);
 
 /* Metric upstream of S^3 (what the reference's example scripts compute with torch before the grid is generated:
  * metric = pt.std(field, dim=1), examples/s3_for_OAT15_airfoil.py:91): temporal mean and standard deviation of every row

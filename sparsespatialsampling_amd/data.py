@@ -112,18 +112,90 @@ class Dataloader:
         self._file_name = value
         self._scan(tolerant=False)
 
-    def load_snapshot(self, field_name: Union[List[str], str],
-                      write_times: Union[str, List[str]] = None) -> Union[List[pt.Tensor], pt.Tensor]:
-        """data matrix ``[N_cells, (N_dims,) N_times]`` of one field (cell-centred values), or a list of them"""
+    def load_snapshot(self, field_name: Union[List[str], str], write_times: Union[str, List[str]] = None,
+                      device: bool = False) -> Union[List[pt.Tensor], pt.Tensor]:
+        """data matrix ``[N_cells, (N_dims,) N_times]`` of one field (cell-centred values), or a list of them, in the loader's
+        ``dtype`` whatever the file stores (float32 or float64 datasets).
+
+        ``device=True`` (this build's addition) returns the matrix ON THE GPU, where ``compute_svd`` and ``DMD`` read it: the
+        datasets go from the file into page-locked memory in their own type, cross the link as they are and are laid out --
+        and converted where the types differ -- by ``hipops.cell_major``.  No host ``stack``, no host conversion; same values."""
         times = self.write_times if write_times is None else write_times
         times = [times] if isinstance(times, str) else list(times)
         fields = [field_name] if isinstance(field_name, str) else list(field_name)
         out = []
         with self._open() as f:
             for name in fields:
+                if device:
+                    out.append(self._load_on_device(f, name, times))
+                    continue
                 per_time = [pt.from_numpy(f.read(f"{DATA}/{t}/{name}_center")) for t in times]
                 out.append(pt.stack(per_time, dim=-1).to(self._dtype))
         return out[0] if len(out) == 1 else out
+
+    DEVICE_GROUP_TIMES = 16       # write times per upload + transpose: 64-byte (float32) / 128-byte (float64) runs per output row
+
+    def _load_on_device(self, f, name: str, times: list) -> pt.Tensor:
+        """one field ``[N, (n_comp,) T]`` on the device.  Groups of ``DEVICE_GROUP_TIMES`` write times (of one storage type):
+        the datasets of group j + 1 are read into one of two page-locked stages while group j is on its way up and being
+        transposed on a stream of its own."""
+        from . import hipops
+        if self._dtype not in hipops.DTYPE_CODE:
+            raise TypeError(f"load_snapshot(device=True) yields float32 or float64, not {self._dtype}")
+        dev = hipops.device()
+        paths = [f"{DATA}/{t}/{name}_center" for t in times]
+        if not paths:
+            raise ValueError("load_snapshot: no write times")
+        shape = tuple(f.shape(paths[0]))
+        types = []
+        for p in paths:
+            kind = f.dtype(p)
+            if tuple(f.shape(p)) != shape or len(shape) not in (1, 2) or kind not in (np.float32, np.float64):
+                raise ValueError(f"load_snapshot(device=True): {p} is {kind}{tuple(f.shape(p))}; float32 / float64 datasets of one "
+                                 f"shape [N] or [N, n_comp] are loaded on the device")
+            types.append(kind)
+        n_t, per = len(paths), int(np.prod(shape, dtype=np.int64))
+        out = pt.empty(shape + (n_t,), dtype=self._dtype, device=dev)
+        if per == 0:
+            return out
+        groups, g0 = [], 0
+        while g0 < n_t:
+            g1 = g0 + 1
+            while g1 < n_t and g1 - g0 < self.DEVICE_GROUP_TIMES and types[g1] == types[g0]:
+                g1 += 1
+            groups.append((g0, g1))
+            g0 = g1
+        widest = max(b - a for a, b in groups)
+        stages, on_device, free = [], [], [None, None]
+        for _ in range(min(2, len(groups))):
+            try:
+                stages.append(pt.empty(widest * per * 8, dtype=pt.uint8, pin_memory=True))
+            except RuntimeError as err:            # page-locked memory refused (limits of the host): pageable then
+                logger.warning(f"no page-locked memory for the loader's stage ({err}): reading through pageable memory.")
+                stages.append(pt.empty(widest * per * 8, dtype=pt.uint8))
+            on_device.append(pt.empty(widest * per * 8, dtype=pt.uint8, device=dev))
+        cur, up = pt.cuda.current_stream(), pt.cuda.Stream()
+        up.wait_stream(cur)
+        out.record_stream(up)
+        for j, (a, b) in enumerate(groups):
+            turn = j % 2
+            if free[turn] is not None:
+                free[turn].synchronize()           # group j - 2 has left this stage (and its device image has been transposed)
+            torch_type = pt.float32 if types[a] == np.float32 else pt.float64
+            host = stages[turn][:(b - a) * per * np.dtype(types[a]).itemsize].view(torch_type).view((b - a,) + shape)
+            image = host.numpy()
+            for i in range(a, b):
+                f.read_into(paths[i], image[i - a])
+            with pt.cuda.stream(up):
+                staged = on_device[turn][:host.numel() * host.element_size()].view(torch_type).view(host.shape)
+                staged.copy_(host, non_blocking=True)
+                hipops.cell_major(staged, out, a)
+                free[turn] = pt.cuda.Event()
+                free[turn].record(up)
+        cur.wait_stream(up)
+        for buf in on_device:
+            buf.record_stream(up)
+        return out
 
 
 # ======================================================================================================================
@@ -144,8 +216,11 @@ _PLACEMENTS = {
 
 
 class Datawriter:
-    def __init__(self, file_path: str, file_name: str, mode: str = "w", mixed: bool = False):
+    def __init__(self, file_path: str, file_name: str, mode: str = "w", mixed: bool = False, file_precision: bool = False):
+        """``file_precision`` (this build's addition, after the reference's arguments): the XDMF file states the precision each
+        attribute's dataset really has (``XDMFWriter``); by default it is the reference's text, which states 8 throughout"""
         self._file_path, self._file_name, self._mode, self._mixed = file_path, file_name, mode, mixed
+        self._file_precision = file_precision
         self._file = open_h5(join(file_path, file_name), mode)
         self._n_cells = None
 
@@ -205,7 +280,7 @@ class Datawriter:
         if not isfile(full):
             raise FileNotFoundError(f"Could not find {full}. Make sure the file exists and the provided path is correct.")
         logger.info(f"Writing XDMF file for file {self._file_name}")
-        XDMFWriter(self._file_path, self._file_name, mixed=self._mixed).write_xdmf()
+        XDMFWriter(self._file_path, self._file_name, mixed=self._mixed, file_precision=self._file_precision).write_xdmf()
 
     @property
     def mode(self) -> str:
@@ -241,12 +316,19 @@ class Datawriter:
 # ======================================================================================================================
 class XDMFWriter:
     """XDMF2 description of an S^3 HDF5 file: a temporal collection, or one uniform grid when there is no ``data`` group.
-    The text is the reference writer's (data.py:566-777); it is assembled here from a shape inventory of the file."""
+    The text is the reference writer's (data.py:566-777); it is assembled here from a shape inventory of the file.
+
+    The reference states ``Precision="8"`` for every attribute, also for one whose dataset a user wrote in single precision
+    (its own writer's output is the fixture of tests/test_export_vs_reference.py).  ``file_precision=True`` states 4 for the
+    attributes whose dataset is float32 instead -- ``ExportData`` asks for it, so that files it wrote with
+    ``file_dtype=float32`` are described as they are; for a file without single-precision fields the text is the same."""
 
     _OPEN = '<?xml version="1.0"?>\n<!DOCTYPE Xdmf SYSTEM "Xdmf.dtd" []>\n<Xdmf Version="2.0">\n'
 
-    def __init__(self, file_path: str, file_name: str, grid_name: str = "grid_s_cube", mixed: bool = False):
+    def __init__(self, file_path: str, file_name: str, grid_name: str = "grid_s_cube", mixed: bool = False,
+                 file_precision: bool = False):
         self._file_path, self._hdf_file_name, self._grid_name, self._mixed = file_path, file_name, grid_name, mixed
+        self._file_precision = file_precision
         self._xdmf_file_name = f"{file_name.split('.h5')[0]}.xdmf"
         self._inventory = self._take_inventory()
         grid = self._inventory[GRID]
@@ -256,8 +338,9 @@ class XDMFWriter:
         self._dims = "XY" if self._n_dimensions == 2 else "XYZ"
 
     def _take_inventory(self) -> dict:
-        """{group: {dataset: shape}} with ``data`` as {time: {dataset: shape}}; raises when the grid is incomplete"""
-        inv = {}
+        """{group: {dataset: shape}} with ``data`` as {time: {dataset: shape}}; raises when the grid is incomplete.  Beside it
+        ``self._single``: the paths of the single-precision datasets under ``constant`` and ``data`` (``file_precision``)"""
+        inv, self._single = {}, set()
         with open_h5(join(self._file_path, self._hdf_file_name), "r") as f:
             top = f.keys()
             if GRID not in top:
@@ -271,6 +354,10 @@ class XDMFWriter:
             inv[CONST] = {k: f.shape(f"{CONST}/{k}") for k in f.keys(CONST)} if CONST in top else None
             inv[DATA] = ({t: {k: f.shape(f"{DATA}/{t}/{k}") for k in f.keys(f"{DATA}/{t}")} for t in f.keys(DATA)}
                          if DATA in top else None)
+            if self._file_precision:
+                attributes = [f"{CONST}/{k}" for k in (inv[CONST] or {})] + [f"{DATA}/{t}/{k}" for t, names in (inv[DATA] or {}).items()
+                                                                              for k in names]
+                self._single = {p for p in attributes if f.dtype(p) == np.float32}
         return inv
 
     # -- text fragments --------------------------------------------------------------------------------------------
@@ -291,8 +378,9 @@ class XDMFWriter:
                            f"{self._n_cells} or the number of vertices with N_vertices = {self._n_vertices}. Skipping this field.")
             return ""
         width = 1 if len(shape) == 1 else shape[1]
+        precision = 4 if h5_key in self._single else 8
         return (f'<Attribute Name="{label}" AttributeType="Vector" Center="{location}">\n<DataItem NumberType="Float" '
-                f'Precision="8" Format="HDF" Dimensions="{shape[0]} {width}">\n{self._hdf_file_name}:/{h5_key}\n</DataItem>\n'
+                f'Precision="{precision}" Format="HDF" Dimensions="{shape[0]} {width}">\n{self._hdf_file_name}:/{h5_key}\n</DataItem>\n'
                 f'</Attribute>\n')
 
     def _constant_fields(self) -> str:

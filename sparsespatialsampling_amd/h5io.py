@@ -165,6 +165,21 @@ class NativeH5File:
         self._check(self._lib.s3h5_shape(self._h, path.encode(), C.byref(dtype), C.byref(ndim), dims), f"shape {path!r}")
         return tuple(dims[i] for i in range(ndim.value))
 
+    def dtype(self, path):
+        """numpy type a dataset is read as: its own where the sink knows it, float64 otherwise (as ``read`` does)"""
+        dtype, ndim, dims = C.c_int(0), C.c_int(0), (C.c_int64 * 8)()
+        self._check(self._lib.s3h5_shape(self._h, path.encode(), C.byref(dtype), C.byref(ndim), dims), f"shape {path!r}")
+        return _TYPES[dtype.value if dtype.value in _TYPES else 1]
+
+    def read_into(self, path, out):
+        """a dataset into the caller's C-contiguous array of the dataset's size (the loader's pinned stage), as ``out``'s type"""
+        if not out.flags.c_contiguous or out.dtype not in _CODES:
+            raise ValueError("read_into: C-contiguous array of a supported type required")
+        if int(np.prod(self.shape(path), dtype=np.int64)) != out.size:
+            raise ValueError(f"read_into: {path!r} does not have the {out.size} elements of the buffer")
+        self._check(self._lib.s3h5_read(self._h, path.encode(), _CODES[out.dtype], out.ctypes.data_as(C.c_void_p), out.size), f"read {path!r}")
+        return out
+
     def read(self, path):
         dtype, ndim, dims = C.c_int(0), C.c_int(0), (C.c_int64 * 8)()
         self._check(self._lib.s3h5_shape(self._h, path.encode(), C.byref(dtype), C.byref(ndim), dims), f"shape {path!r}")
@@ -230,6 +245,13 @@ class H5pyFile:
 
     def shape(self, path):
         return tuple(self._f[path].shape)
+
+    def dtype(self, path):
+        return np.dtype(self._f[path].dtype)
+
+    def read_into(self, path, out):
+        out.reshape(-1)[...] = np.asarray(self._f[path][()]).reshape(-1)
+        return out
 
     def read(self, path):
         return self._f[path][()]

@@ -304,25 +304,93 @@ def yard_stream(src, dst, reads, writes, nontemporal=True):
     return r.value, w.value
 
 
-def snapshot_major(values, n_comp, n_snapshots, out=None):
-    """device [nc, n_comp*T] (or [nc, n_comp, T]) f64 -> device [T, nc, n_comp]: contiguous snapshots for the HDF5 sink"""
-    nc = int(values.shape[0])
+def _batch_values(values, n_comp, n_snapshots, who):
+    """checks of the interpolated batch ``[nc, n_comp*T]`` / ``[nc, n_comp, T]`` the transposes read; -> nc"""
+    if not (isinstance(values, pt.Tensor) and values.is_cuda and values.is_contiguous() and values.dtype == pt.float64):
+        raise TypeError(f"{who}: contiguous float64 device tensor required as input")
+    n_comp, n_snapshots = int(n_comp), int(n_snapshots)
+    if values.dim() < 1 or n_comp < 1 or n_snapshots < 0 or values.numel() != int(values.shape[0]) * n_comp * n_snapshots:
+        raise ValueError(f"{who}: a batch of shape {tuple(values.shape)} does not hold {n_comp} component(s) x {n_snapshots} snapshot(s) per row")
+    return int(values.shape[0])
+
+
+def _storage_dtype(dtype, who):
+    if dtype is None:
+        return pt.float64
+    if dtype not in DTYPE_CODE:
+        raise ValueError(f"{who}: the storage type is float32 or float64, not {dtype}")
+    return dtype
+
+
+def snapshot_major(values, n_comp, n_snapshots, out=None, dtype=None):
+    """device [nc, n_comp*T] (or [nc, n_comp, T]) f64 -> device [T, nc, n_comp]: contiguous snapshots for the HDF5 sink.
+    ``dtype`` (default float64): the storage type of the result; float32 rounds every value once, to nearest even, exactly as
+    ``numpy.astype(float32)`` does (s3_snapshot_major_as)."""
+    dtype = _storage_dtype(dtype, "snapshot_major")
+    nc = _batch_values(values, n_comp, n_snapshots, "snapshot_major")
     if out is None:
-        out = pt.empty((int(n_snapshots), nc, int(n_comp)), dtype=pt.float64, device=values.device)
-    elif not (out.is_cuda and out.is_contiguous() and out.dtype == pt.float64 and out.numel() == values.numel()):
-        raise TypeError("snapshot_major: contiguous float64 device tensor of the batch's size required as out")
-    check(_lib.hip_lib().s3_snapshot_major(_ptr(values), nc, int(n_comp), int(n_snapshots), _ptr(out), _stream()),
-          "s3_snapshot_major")
+        out = pt.empty((int(n_snapshots), nc, int(n_comp)), dtype=dtype, device=values.device)
+    elif not (out.is_cuda and out.is_contiguous() and out.dtype == dtype and out.numel() == values.numel()
+              and out.device == values.device):
+        raise TypeError(f"snapshot_major: contiguous {dtype} device tensor of the batch's size required as out")
+    if dtype == pt.float64:
+        check(_lib.hip_lib().s3_snapshot_major(_ptr(values), nc, int(n_comp), int(n_snapshots), _ptr(out), _stream()),
+              "s3_snapshot_major")
+    else:
+        check(_lib.hip_lib().s3_snapshot_major_as(_ptr(values), nc, int(n_comp), int(n_snapshots), DTYPE_CODE[dtype], _ptr(out),
+                                                  _stream()), "s3_snapshot_major_as")
     return out
 
 
-def snapshot_major_rows(values, n_comp, n_snapshots, rows, n_out, out_ptr):
+def snapshot_major_rows(values, n_comp, n_snapshots, rows, n_out, out_ptr, dtype=None):
     """a shard's values, device [n_mine, n_comp*T] f64, -> rows ``rows`` (device int32 [n_mine]) of the snapshot-major batch
-    buffer ``[T, n_out, n_comp]`` at device address ``out_ptr`` (host memory all ranks share, s3_snapshot_major_rows)"""
-    if not (rows.is_cuda and rows.dtype == pt.int32 and rows.is_contiguous() and rows.numel() == values.shape[0]):
+    buffer ``[T, n_out, n_comp]`` of ``dtype`` (default float64) at device address ``out_ptr`` (host memory all ranks share,
+    s3_snapshot_major_rows).  The caller answers for the row ids lying in ``[0, n_out)`` and for the buffer's size."""
+    dtype = _storage_dtype(dtype, "snapshot_major_rows")
+    nc = _batch_values(values, n_comp, n_snapshots, "snapshot_major_rows")
+    if not (isinstance(rows, pt.Tensor) and rows.is_cuda and rows.dtype == pt.int32 and rows.is_contiguous() and rows.numel() == nc):
         raise TypeError("snapshot_major_rows: one int32 device row id per input row required")
-    check(_lib.hip_lib().s3_snapshot_major_rows(_ptr(values), int(values.shape[0]), int(n_comp), int(n_snapshots), _ptr(rows),
-                                                int(n_out), C.c_void_p(int(out_ptr)), _stream()), "s3_snapshot_major_rows")
+    if int(n_out) < nc or not int(out_ptr) or int(out_ptr) % (4 if dtype == pt.float32 else 8):
+        raise ValueError(f"snapshot_major_rows: an output of {n_out} rows at address {int(out_ptr):#x} cannot take {nc} rows of {dtype}")
+    if dtype == pt.float64:
+        check(_lib.hip_lib().s3_snapshot_major_rows(_ptr(values), nc, int(n_comp), int(n_snapshots), _ptr(rows),
+                                                    int(n_out), C.c_void_p(int(out_ptr)), _stream()), "s3_snapshot_major_rows")
+    else:
+        check(_lib.hip_lib().s3_snapshot_major_rows_as(_ptr(values), nc, int(n_comp), int(n_snapshots), _ptr(rows), int(n_out),
+                                                       DTYPE_CODE[dtype], C.c_void_p(int(out_ptr)), _stream()),
+              "s3_snapshot_major_rows_as")
+
+
+def cell_major(snapshots, out, t0=0):
+    """datasets as the file holds them, device ``[T_b, nc]`` or ``[T_b, nc, n_comp]`` float32 / float64 (contiguous), -> columns
+    ``[t0, t0 + T_b)`` of the cell-major device matrix ``out`` ``[nc, T]`` / ``[nc, n_comp, T]`` float32 / float64 that SVD and DMD
+    read (s3_cell_major).  ``out`` has unit stride along T and one pitch for all its (cell, component) rows; its other columns
+    and the padding of its rows are left alone.  float64 -> float32 rounds to nearest even, float32 -> float64 is exact."""
+    for name, t in (("snapshots", snapshots), ("out", out)):
+        if not (isinstance(t, pt.Tensor) and t.is_cuda and t.dtype in DTYPE_CODE):
+            raise TypeError(f"cell_major: {name} must be a float32 or float64 device tensor")
+    if snapshots.device != out.device:
+        raise TypeError("cell_major: snapshots and out live on different devices")
+    if not snapshots.is_contiguous():
+        raise TypeError("cell_major: contiguous snapshots required")
+    if snapshots.dim() not in (2, 3) or out.dim() != snapshots.dim():
+        raise ValueError(f"cell_major: snapshots [T_b, nc(, n_comp)] and out [nc(, n_comp), T] required, got {tuple(snapshots.shape)} "
+                         f"and {tuple(out.shape)}")
+    t_b, nc = int(snapshots.shape[0]), int(snapshots.shape[1])
+    n_comp = int(snapshots.shape[2]) if snapshots.dim() == 3 else 1
+    n_cols, t0 = int(out.shape[-1]), int(t0)
+    if tuple(out.shape[:-1]) != tuple(snapshots.shape[1:]):
+        raise ValueError(f"cell_major: out {tuple(out.shape)} does not match snapshots {tuple(snapshots.shape)}")
+    if t0 < 0 or t0 + t_b > n_cols:
+        raise ValueError(f"cell_major: columns [{t0}, {t0 + t_b}) lie outside the {n_cols} columns of out")
+    if nc == 0 or t_b == 0:
+        return out
+    pitch = int(out.stride(0)) if n_comp == 1 else int(out.stride(-2))          # (the stride of an axis of length 1 says nothing)
+    if out.stride(-1) != 1 or pitch < n_cols or (out.dim() == 3 and n_comp > 1 and int(out.stride(0)) != n_comp * pitch):
+        raise ValueError("cell_major: out needs unit stride along T and one pitch >= T for all its rows")
+    check(_lib.hip_lib().s3_cell_major(C.c_void_p(snapshots.data_ptr()), DTYPE_CODE[snapshots.dtype], t_b, nc, n_comp,
+                                       C.c_void_p(out.data_ptr()), DTYPE_CODE[out.dtype], n_cols, pitch, t0, _stream()), "s3_cell_major")
+    return out
 
 
 class InterpPlan:
