@@ -1,7 +1,8 @@
 """The typed Gram / tall-GEMM entry points (s3_gram, s3_tall_gemm: csrc/svd.hip) and the DMD built on them
 (sparsespatialsampling_amd/dmd.py) on the GPU: bit parity between float32 input and its float64 copy and between the new and the
 float64-only entry points, long-double sums per element, canaries, and the DMD of every case of tests/dmd_cases.py against the
-direct CPU reference and the planted dynamics."""
+direct CPU reference and the planted dynamics; the centred / weighted forms (s3_weighted_gram, s3_gram with mean and weight,
+s3_centered_gemm with lmean and with minus_from) per element against long double within the bounds of tests/centered_cases.py."""
 import ctypes as C
 import logging
 
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 import torch as pt
 
+from tests import centered_cases as cc
 from tests import dmd_cases as dc
 
 pytestmark = pytest.mark.gpu
@@ -324,3 +326,74 @@ def test_dmd_of_float32_needs_less_extra_memory_than_a_double_copy():
     extra = pt.cuda.max_memory_allocated() - before
     print(f"extra peak {extra} bytes, a float64 copy {data.numel() * 8} bytes")
     assert model.svd.rank == case.r and extra < data.numel() * 8
+
+
+# ---- centred and weighted Gram, centred and residual GEMM: per element against long double -----------------------------------------
+WORST = {}
+
+
+def note(family, r):
+    WORST[family] = max(WORST.get(family, 0.0), r)
+    return r
+
+
+@pytest.mark.parametrize("t", SHAPES_T)
+@pytest.mark.parametrize("n", SHAPES_N)
+def test_centred_weighted_gram_per_element(ops, n, t):
+    """rows of mean 1e5 and fluctuation 1e-2, weights from 1e-6 to 1e2, both dtypes, mean and weight / mean alone / weight alone: every
+    element within (N + 8) u sum_n a_n |d_ni| |d_nj| of the long-double sum over d = x - mean with the doubles the kernel is given; every
+    layout and offset gives the same bits; float64 input through s3_weighted_gram gives them too"""
+    from sparsespatialsampling_amd import svd
+    for dtype in (np.float32, np.float64):
+        x = cc.rows(n, t, dtype, 7 * n + t)
+        mean, weight = cc.row_means(x), cc.weights(n, n + t)
+        xt, md, wd = pt.from_numpy(x), pt.from_numpy(mean).cuda(), pt.from_numpy(weight).cuda()
+        forms = [(mean, weight), (mean, None) if dtype == np.float32 else (None, weight)]
+        for m_host, w_host in forms:
+            m_dev, w_dev = (md if m_host is not None else None), (wd if w_host is not None else None)
+            ref, mag = cc.gram_reference(x, m_host, w_host)
+            want = ops.gram(device_matrix(xt, "contiguous"), m_dev, w_dev)
+            r = note("gram", cc.ratio(want.cpu().numpy(), ref, cc.gram_bound(n, mag)))
+            assert r <= 1.0, (np.dtype(dtype).name, m_host is None, w_host is None, r)
+            assert same_bits(want, want.T.contiguous())
+            for layout in LAYOUTS:
+                for offset in (0, 1):
+                    assert same_bits(ops.gram(device_matrix(xt, layout, offset), m_dev, w_dev), want), (layout, offset)
+            if dtype == np.float64 and m_host is not None and w_host is not None:
+                for layout in LAYOUTS:
+                    assert same_bits(svd.weighted_gram(device_matrix(xt, layout, 1), md, wd), want), layout
+    print(f"worst |error| / bound so far: {WORST}")
+
+
+@pytest.mark.parametrize("n", [1, 4, 64, 65, 80])
+@pytest.mark.parametrize("m", [1, 15, 17, 257])
+def test_centred_and_residual_gemm_per_element(ops, m, n):
+    """(L - lmean) B within (k + 4) u sum |l - lmean| |b| per element; (E - emean) - (L - lmean) B within that plus
+    2 u |e - emean| + u |c_ref|; with and without each mean; L and E in every layout and offset (same bits)"""
+    from sparsespatialsampling_amd import svd
+    for k in (3, 17, 130):
+        rng = np.random.default_rng(m + 31 * n + k)
+        left, e = cc.rows(m, k, np.float64, m + 31 * n + k), cc.rows(m, n, np.float64, 5 + m + n)
+        lmean, emean = cc.row_means(left), cc.row_means(e) + 1e-3 * rng.standard_normal(m)
+        b = rng.standard_normal((k, n))
+        lt, et, bd = pt.from_numpy(left), pt.from_numpy(e), pt.from_numpy(b).cuda()
+        lmd, emd = pt.from_numpy(lmean).cuda(), pt.from_numpy(emean).cuda()
+        for lm_host, lm_dev in ((lmean, lmd), (None, None)):
+            ref, bound = cc.gemm_reference(left, lm_host, b)
+            want = svd.centered_gemm(device_matrix(lt, "contiguous"), lm_dev, bd)
+            r = note("gemm", cc.ratio(want.cpu().numpy(), ref, bound))
+            assert want.shape == (m, n) and r <= 1.0, (k, lm_host is None, r)
+            for em_host, em_dev in ((emean, emd), (None, None)):
+                ref_r, bound_r = cc.gemm_reference(left, lm_host, b, e, em_host)
+                want_r = svd.centered_gemm(device_matrix(lt, "contiguous"), lm_dev, bd, minus_from=device_matrix(et, "contiguous"),
+                                           minus_from_mean=em_dev)
+                r = note("residual gemm", cc.ratio(want_r.cpu().numpy(), ref_r, bound_r))
+                assert r <= 1.0, (k, lm_host is None, em_host is None, r)
+                if lm_host is None or em_host is None:
+                    continue
+                for layout in LAYOUTS:
+                    for offset in (0, 1):
+                        ld, ed = device_matrix(lt, layout, offset), device_matrix(et, layout, 1 - offset)
+                        assert same_bits(svd.centered_gemm(ld, lm_dev, bd), want), (k, layout, offset)
+                        assert same_bits(svd.centered_gemm(ld, lm_dev, bd, minus_from=ed, minus_from_mean=em_dev), want_r), (k, layout, offset)
+    print(f"worst |error| / bound so far: {WORST}")
