@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "dev_buf.h"
 #include "s3hip.h"
 #include "topo_core.h"
 
@@ -14,12 +15,29 @@ namespace s3 {
 
 void set_error(const char *fmt, ...);
 
+// device memory of DevBuf (csrc/dev_buf.h): the runtime's allocator as it is, no pool, no stream order
+struct HipMem {
+    static int alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void free(void *p) { (void)hipFree(p); }
+};
+
+// (the cast: DevBuf::alloc hands the allocator's status on as an int)
 #define S3_HIP_CHECK(expr)                                                                       \
     do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
+        const hipError_t _e = static_cast<hipError_t>(expr);                                     \
         if (_e != hipSuccess) {                                                                  \
             s3::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
             return _e == hipErrorNoDevice || _e == hipErrorInvalidDevice ? S3_ENODEV : S3_EHIP;  \
+        }                                                                                        \
+    } while (0)
+
+// for the sites that tell the caller when the device is out of memory (construction of an index, a plan, an engine)
+#define S3_HIP_CHECK_MEM(expr)                                                                   \
+    do {                                                                                         \
+        const hipError_t _e = static_cast<hipError_t>(expr);                                     \
+        if (_e != hipSuccess) {                                                                  \
+            s3::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+            return _e == hipErrorOutOfMemory ? S3_ENOMEM : S3_EHIP;                              \
         }                                                                                        \
     } while (0)
 

@@ -26,23 +26,25 @@
 
 #include <algorithm>
 #include <exception>
+#include <memory>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 struct s3_interp_plan : s3::PlanTables {
     int64_t nc = 0, n_src = 0;
     int k = 0, ucap = 0, tc = 64;
-    double *wp = nullptr;                // [nc*k] weights in the layout of `loc`: per tile [m][cell in tile]
+    s3::DevBuf<double> wp;               // [nc*k] weights in the layout of `loc`: per tile [m][cell in tile]
     bool has_weights = false;
-    double *dump = nullptr;              // per-lane slots for the stores the persistent kernel must not make
+    s3::DevBuf<double> dump;             // per-lane slots for the stores the persistent kernel must not make
     size_t dump_doubles = 0;
-    int32_t *rows_src = nullptr;         // [total_rows] `rows` as row ids of the caller's full table (s3_interp_plan_set_source_ids)
+    s3::DevBuf<int32_t> rows_src;        // [total_rows] `rows` as row ids of the caller's full table (s3_interp_plan_set_source_ids)
     int64_t n_table = 0;                 // rows of that table
-    int32_t *sched_begin = nullptr;      // [sched_wgs + 1] tile lists of the persistent workgroups (plan_schedule)
-    int32_t *sched_tiles = nullptr;      // [n_tiles]
-    int4 *sched_desc = nullptr;          // [n_tiles] in list order: {first row, rows, first cell, cells} of each scheduled tile
-    double *wl = nullptr;                // the weights and
-    uint16_t *pl = nullptr;              // positions again, in the order the persistent kernel's LANES take them (lane_tables_*)
+    s3::DevBuf<int32_t> sched_begin;     // [sched_wgs + 1] tile lists of the persistent workgroups (plan_schedule)
+    s3::DevBuf<int32_t> sched_tiles;     // [n_tiles]
+    s3::DevBuf<int4> sched_desc;         // [n_tiles] in list order: {first row, rows, first cell, cells} of each scheduled tile
+    s3::DevBuf<double> wl;               // the weights and
+    s3::DevBuf<uint16_t> pl;             // positions again, in the order the persistent kernel's LANES take them (lane_tables_*)
     int sched_wgs = 0;
 };
 
@@ -1205,34 +1207,23 @@ static int plan_schedule(s3_interp_plan *p, hipStream_t st) {
     }
     // built into locals and handed to the plan only when every step has succeeded: a failure half way (a transient out-of-memory)
     // must not leave a plan whose next launch skips this function and runs with a grid of 0 workgroups and null tables
-    int32_t *d_tiles = nullptr, *d_begin = nullptr;
-    int4 *d_desc = nullptr;
-    uint16_t *d_pl = nullptr;
-    auto build = [&]() -> int {
-        S3_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d_tiles), sizeof(int32_t) * std::max<size_t>(nt, 1)));
-        S3_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d_begin), sizeof(int32_t) * ((size_t)wgs + 1)));
-        S3_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d_pl), sizeof(uint16_t) * (size_t)p->nc * 32));
-        lane_positions_kernel<<<(unsigned)p->n_tiles, 256, 0, st>>>(p->tile_cell_begin, p->loc, p->k, d_pl);
-        S3_LAUNCH_CHECK();
-        S3_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d_desc), sizeof(int4) * desc.size()));
-        S3_HIP_CHECK(hipMemcpyAsync(d_desc, desc.data(), sizeof(int4) * desc.size(), hipMemcpyHostToDevice, st));
-        S3_HIP_CHECK(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, st));
-        S3_HIP_CHECK(hipMemcpyAsync(d_begin, begin.data(), sizeof(int32_t) * ((size_t)wgs + 1), hipMemcpyHostToDevice, st));
-        S3_HIP_CHECK(hipStreamSynchronize(st));
-        return S3_OK;
-    };
-    const int rc = build();
-    if (rc != S3_OK) {
-        if (d_tiles) (void)hipFree(d_tiles);
-        if (d_begin) (void)hipFree(d_begin);
-        if (d_pl) (void)hipFree(d_pl);
-        if (d_desc) (void)hipFree(d_desc);
-        return rc;
-    }
-    p->sched_tiles = d_tiles;
-    p->sched_begin = d_begin;
-    p->pl = d_pl;
-    p->sched_desc = d_desc;
+    DevBuf<int32_t> d_tiles, d_begin;
+    DevBuf<int4> d_desc;
+    DevBuf<uint16_t> d_pl;
+    S3_HIP_CHECK(d_tiles.alloc(nt));
+    S3_HIP_CHECK(d_begin.alloc((size_t)wgs + 1));
+    S3_HIP_CHECK(d_pl.alloc((size_t)p->nc * 32));
+    lane_positions_kernel<<<(unsigned)p->n_tiles, 256, 0, st>>>(p->tile_cell_begin, p->loc, p->k, d_pl);
+    S3_LAUNCH_CHECK();
+    S3_HIP_CHECK(d_desc.alloc(desc.size()));
+    S3_HIP_CHECK(hipMemcpyAsync(d_desc, desc.data(), sizeof(int4) * desc.size(), hipMemcpyHostToDevice, st));
+    S3_HIP_CHECK(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, st));
+    S3_HIP_CHECK(hipMemcpyAsync(d_begin, begin.data(), sizeof(int32_t) * ((size_t)wgs + 1), hipMemcpyHostToDevice, st));
+    S3_HIP_CHECK(hipStreamSynchronize(st));
+    p->sched_tiles = std::move(d_tiles);
+    p->sched_begin = std::move(d_begin);
+    p->pl = std::move(d_pl);
+    p->sched_desc = std::move(d_desc);
     p->sched_wgs = wgs;
     return S3_OK;
 }
@@ -1261,10 +1252,8 @@ static int launch_stream_e(s3_interp_plan *p, const int32_t *rows, const void *d
     const size_t lds = (size_t)LAY::NPASS * (256 / LAY::LPR) * LAY::LP * 16 + 2 * 256 * sizeof(int32_t);
     const size_t dump_doubles = (size_t)p->sched_wgs * 256 * 2;        // one 16-byte slot per lane of the launch
     if (p->dump_doubles < dump_doubles) {
-        if (p->dump) (void)hipFree(p->dump);
-        p->dump = nullptr;
         p->dump_doubles = 0;
-        S3_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&p->dump), dump_doubles * sizeof(double)));
+        S3_HIP_CHECK(p->dump.alloc(dump_doubles));
         p->dump_doubles = dump_doubles;
     }
 #define S3_LAUNCH_STREAM(K)                                                                                                   \
@@ -1545,23 +1534,7 @@ plan_loads_kernel(const int32_t *__restrict__ tile_row_begin, const int32_t *__r
 
 extern "C" {
 
-void s3_interp_plan_destroy(s3_interp_plan *p) {
-    if (!p) return;
-    if (p->perm) (void)hipFree(p->perm);
-    if (p->tile_cell_begin) (void)hipFree(p->tile_cell_begin);
-    if (p->tile_row_begin) (void)hipFree(p->tile_row_begin);
-    if (p->rows) (void)hipFree(p->rows);
-    if (p->loc) (void)hipFree(p->loc);
-    if (p->wp) (void)hipFree(p->wp);
-    if (p->dump) (void)hipFree(p->dump);
-    if (p->rows_src) (void)hipFree(p->rows_src);
-    if (p->sched_begin) (void)hipFree(p->sched_begin);
-    if (p->sched_tiles) (void)hipFree(p->sched_tiles);
-    if (p->sched_desc) (void)hipFree(p->sched_desc);
-    if (p->wl) (void)hipFree(p->wl);
-    if (p->pl) (void)hipFree(p->pl);
-    delete p;
-}
+void s3_interp_plan_destroy(s3_interp_plan *p) { delete p; }
 
 int s3_interp_plan_create(const int32_t *d_idx, int64_t nc, int k, int64_t n_src, const double *d_centers, int dim,
                           int tile_cells, s3_stream stream, s3_interp_plan **out) try {
@@ -1578,21 +1551,15 @@ int s3_interp_plan_create(const int32_t *d_idx, int64_t nc, int k, int64_t n_src
     S3_REQUIRE(nc * (int64_t)k < ((int64_t)1 << 31), "s3_interp_plan_create: table too large");
     hipStream_t st = as_stream(stream);
 
-    s3_interp_plan *p = new s3_interp_plan();
+    std::unique_ptr<s3_interp_plan> p(new s3_interp_plan());
     p->nc = nc; p->k = k; p->ucap = plan_ucap(k, PL_TC); p->tc = PL_TC; p->n_src = n_src;
-    const int rc = build_plan_tables(d_idx, nc, k, n_src, d_centers, dim, PL_TC, p->ucap, st, p);
-    if (rc != S3_OK) {
-        s3_interp_plan_destroy(p);
-        return rc;
+    const int rc = build_plan_tables(d_idx, nc, k, n_src, d_centers, dim, PL_TC, p->ucap, st, p.get());
+    if (rc != S3_OK) return rc;
+    if (stream_can_take(p.get())) {          // tile lists of the persistent kernel
+        const int rs = plan_schedule(p.get(), st);
+        if (rs != S3_OK) return rs;
     }
-    if (stream_can_take(p)) {                // tile lists of the persistent kernel
-        const int rs = plan_schedule(p, st);
-        if (rs != S3_OK) {
-            s3_interp_plan_destroy(p);
-            return rs;
-        }
-    }
-    *out = p;
+    *out = p.release();
     return S3_OK;
 } catch (const std::exception &e) {      // host-side allocations of the builder
     s3::set_error("s3_interp_plan_create: %s", e.what());
@@ -1680,26 +1647,12 @@ int s3_interp_plan_cost_profile(const s3_interp_plan *p, int n_samples, double *
 
 int s3_interp_plan_set_weights(s3_interp_plan *p, const double *d_w, s3_stream stream) {
     S3_REQUIRE(p != nullptr && d_w != nullptr, "s3_interp_plan_set_weights: null argument");
-    if (!p->wp) {
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->wp), sizeof(double) * (size_t)p->nc * p->k);
-        if (e != hipSuccess) {
-            p->wp = nullptr;
-            s3::set_error("s3_interp_plan_set_weights: hipMalloc failed: %s", hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? S3_ENOMEM : S3_EHIP;
-        }
-    }
+    if (!p->wp) S3_HIP_CHECK_MEM(p->wp.alloc((size_t)p->nc * p->k));
     permute_weights_kernel<<<(unsigned)p->n_tiles, 256, 0, as_stream(stream)>>>(p->perm, p->tile_cell_begin, d_w, p->k, p->wp);
     S3_LAUNCH_CHECK();
     if (stream_can_take(p)) {                // the persistent kernel's copy, in lane order
         const int nv = ((p->k + 3) / 4 + 1) / 2;
-        if (!p->wl) {
-            const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->wl), sizeof(double) * (size_t)p->nc * 4 * nv * 2);
-            if (e != hipSuccess) {
-                p->wl = nullptr;
-                s3::set_error("s3_interp_plan_set_weights: hipMalloc failed: %s", hipGetErrorString(e));
-                return e == hipErrorOutOfMemory ? S3_ENOMEM : S3_EHIP;
-            }
-        }
+        if (!p->wl) S3_HIP_CHECK_MEM(p->wl.alloc((size_t)p->nc * 4 * nv * 2));
         lane_weights_kernel<<<(unsigned)p->n_tiles, 256, 0, as_stream(stream)>>>(p->tile_cell_begin, p->wp, p->k, p->wl);
         S3_LAUNCH_CHECK();
     }
@@ -1770,21 +1723,19 @@ int s3_interp_plan_set_source_ids(s3_interp_plan *p, const int32_t *d_ids, int64
     S3_REQUIRE(p != nullptr && d_ids != nullptr, "s3_interp_plan_set_source_ids: null argument");
     S3_REQUIRE(n_table_rows >= 1 && n_table_rows < ((int64_t)1 << 31), "s3_interp_plan_set_source_ids: bad table size");
     hipStream_t st = as_stream(stream);
-    if (!p->rows_src)
-        S3_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&p->rows_src), sizeof(int32_t) * (size_t)std::max<int64_t>(p->total_rows, 1)));
+    if (!p->rows_src) S3_HIP_CHECK(p->rows_src.alloc((size_t)p->total_rows));
     p->n_table = 0;
-    int32_t *d_bad = nullptr, bad = 0;
-    S3_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d_bad), sizeof(int32_t)));
-    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(int32_t), st);
-    if (e == hipSuccess && p->total_rows > 0) {
+    DevBuf<int32_t> d_bad;
+    int32_t bad = 0;
+    S3_HIP_CHECK(d_bad.alloc(1));
+    S3_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int32_t), st));
+    if (p->total_rows > 0) {
         source_ids_kernel<<<s3::grid_for(p->total_rows, 256), 256, 0, st>>>(p->rows, p->total_rows, d_ids, (int32_t)n_table_rows,
                                                                             p->rows_src, d_bad);
-        e = hipGetLastError();
+        S3_LAUNCH_CHECK();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d_bad);
-    S3_HIP_CHECK(e);
+    S3_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    S3_HIP_CHECK(hipStreamSynchronize(st));
     S3_REQUIRE(bad == 0, "s3_interp_plan_set_source_ids: id outside [0, %lld)", (long long)n_table_rows);
     p->n_table = n_table_rows;
     return S3_OK;

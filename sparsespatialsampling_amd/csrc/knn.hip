@@ -23,6 +23,7 @@
 #include <cfloat>
 #include <cstdlib>
 #include <cmath>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -33,14 +34,14 @@ struct s3_knn {
     double lo[3] = {0, 0, 0}, h[3] = {1, 1, 1}, inv_h[3] = {1, 1, 1};
     int res[3] = {1, 1, 1};
     int64_t ncell = 1;
-    double *pts = nullptr;         // [n][dim] bucket order
-    int32_t *orig = nullptr;       // [n]
-    int32_t *cell_start = nullptr; // [ncell+1]
-    double *y = nullptr;           // [n] bucket order (optional)
+    s3::DevBuf<double> pts;          // [n][dim] bucket order
+    s3::DevBuf<int32_t> orig;        // [n]
+    s3::DevBuf<int32_t> cell_start;  // [ncell+1]
+    s3::DevBuf<double> y;            // [n] bucket order (optional)
     // second level: buckets holding more than `split` points carry their own r x r (x r) sub-lattice
-    uint8_t *sub_res = nullptr;    // [ncell] 0 = plain bucket, else r
-    int32_t *sub_off = nullptr;    // [ncell] offset of the bucket's table in sub_start
-    int32_t *sub_start = nullptr;  // pooled tables, r^dim + 1 absolute positions each
+    s3::DevBuf<uint8_t> sub_res;     // [ncell] 0 = plain bucket, else r
+    s3::DevBuf<int32_t> sub_off;     // [ncell] offset of the bucket's table in sub_start
+    s3::DevBuf<int32_t> sub_start;   // pooled tables, r^dim + 1 absolute positions each
     int64_t n_refined = 0;
 };
 
@@ -68,7 +69,7 @@ static Grid<DIM> make_grid(const s3_knn *k) {
         g.inv_h[j] = k->inv_h[j];
         g.res[j] = k->res[j];
     }
-    g.sub_res = k->n_refined > 0 ? k->sub_res : nullptr;
+    g.sub_res = k->n_refined > 0 ? k->sub_res.get() : nullptr;
     g.sub_off = k->sub_off;
     g.sub_start = k->sub_start;
     return g;
@@ -1521,15 +1522,15 @@ int s3_knn_create(const double *d_pts, int64_t n, int dim, double target_occupan
 
     // bounding box
     const int nb = 256;
-    double *d_partial = nullptr;
-    S3_HIP_CHECK(hipMalloc(&d_partial, sizeof(double) * nb * 6));
-    bbox_kernel<<<nb, 256, 0, st>>>(d_pts, n, dim, d_partial);
     std::vector<double> part(nb * 6);
-    hipError_t e_bbox = hipGetLastError();
-    if (e_bbox == hipSuccess) e_bbox = hipMemcpyAsync(part.data(), d_partial, sizeof(double) * nb * 6, hipMemcpyDeviceToHost, st);
-    if (e_bbox == hipSuccess) e_bbox = hipStreamSynchronize(st);
-    (void)hipFree(d_partial);
-    S3_HIP_CHECK(e_bbox);
+    {
+        DevBuf<double> d_partial;
+        S3_HIP_CHECK(d_partial.alloc(nb * 6));
+        bbox_kernel<<<nb, 256, 0, st>>>(d_pts, n, dim, d_partial);
+        S3_LAUNCH_CHECK();
+        S3_HIP_CHECK(hipMemcpyAsync(part.data(), d_partial, sizeof(double) * nb * 6, hipMemcpyDeviceToHost, st));
+        S3_HIP_CHECK(hipStreamSynchronize(st));
+    }
     double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
     for (int b = 0; b < nb; ++b)
         for (int j = 0; j < dim; ++j) {
@@ -1539,7 +1540,8 @@ int s3_knn_create(const double *d_pts, int64_t n, int dim, double target_occupan
     for (int j = 0; j < dim; ++j)
         S3_REQUIRE(std::isfinite(lo[j]) && std::isfinite(hi[j]), "s3_knn_create: non-finite coordinates");
 
-    s3_knn *k = new s3_knn();
+    std::unique_ptr<s3_knn> owner(new s3_knn());
+    s3_knn *k = owner.get();
     k->dim = dim;
     k->n = n;
     k->device = dev;
@@ -1569,93 +1571,61 @@ int s3_knn_create(const double *d_pts, int64_t n, int dim, double target_occupan
     }
     k->ncell = ncell;
 
-    int32_t *cid = nullptr, *cursor = nullptr, *scan_tmp = nullptr;
     const int64_t nscan = ncell + 1;
-    auto fail = [&](int rc) {
-        if (cid) (void)hipFree(cid);
-        if (cursor) (void)hipFree(cursor);
-        if (scan_tmp) (void)hipFree(scan_tmp);
-        s3_knn_destroy(k);
-        return rc;
-    };
-#define S3_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            s3::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);  \
-            return fail(_e == hipErrorOutOfMemory ? S3_ENOMEM : S3_EHIP);                              \
-        }                                                                                              \
-    } while (0)
-    S3_TRY(hipMalloc(&k->pts, sizeof(double) * n * dim));
-    S3_TRY(hipMalloc(&k->orig, sizeof(int32_t) * n));
-    S3_TRY(hipMalloc(&k->cell_start, sizeof(int32_t) * nscan));
-    S3_TRY(hipMalloc(&cid, sizeof(int32_t) * n));
-    S3_TRY(hipMalloc(&cursor, sizeof(int32_t) * ncell));
-    S3_TRY(hipMalloc(&scan_tmp, sizeof(int32_t) * scan_tmp_items(nscan)));
-    S3_TRY(hipMemsetAsync(k->cell_start, 0, sizeof(int32_t) * nscan, st));
-    S3_TRY(hipMemsetAsync(cursor, 0, sizeof(int32_t) * ncell, st));
-    if (dim == 2)
-        cell_count_kernel<2><<<grid_for(n, 256), 256, 0, st>>>(make_grid<2>(k), d_pts, n, cid, k->cell_start);
-    else
-        cell_count_kernel<3><<<grid_for(n, 256), 256, 0, st>>>(make_grid<3>(k), d_pts, n, cid, k->cell_start);
-    S3_TRY(hipGetLastError());
-    S3_TRY(exclusive_scan<int32_t>(k->cell_start, k->cell_start, nscan, scan_tmp, st));
-    if (dim == 2)
-        scatter_kernel<2><<<grid_for(n, 256), 256, 0, st>>>(d_pts, n, cid, k->cell_start, cursor, k->pts, k->orig);
-    else
-        scatter_kernel<3><<<grid_for(n, 256), 256, 0, st>>>(d_pts, n, cid, k->cell_start, cursor, k->pts, k->orig);
-    S3_TRY(hipGetLastError());
-    S3_TRY(hipStreamSynchronize(st));
-    (void)hipFree(cid);
-    (void)hipFree(cursor);
-    (void)hipFree(scan_tmp);
-#undef S3_TRY
+    {   // first level; its temporaries are gone before the second level allocates
+        DevBuf<int32_t> cid, cursor, scan_tmp;
+        S3_HIP_CHECK_MEM(k->pts.alloc((size_t)n * dim));
+        S3_HIP_CHECK_MEM(k->orig.alloc((size_t)n));
+        S3_HIP_CHECK_MEM(k->cell_start.alloc((size_t)nscan));
+        S3_HIP_CHECK_MEM(cid.alloc((size_t)n));
+        S3_HIP_CHECK_MEM(cursor.alloc((size_t)ncell));
+        S3_HIP_CHECK_MEM(scan_tmp.alloc(scan_tmp_items(nscan)));
+        S3_HIP_CHECK_MEM(hipMemsetAsync(k->cell_start, 0, sizeof(int32_t) * nscan, st));
+        S3_HIP_CHECK_MEM(hipMemsetAsync(cursor, 0, sizeof(int32_t) * ncell, st));
+        if (dim == 2)
+            cell_count_kernel<2><<<grid_for(n, 256), 256, 0, st>>>(make_grid<2>(k), d_pts, n, cid, k->cell_start);
+        else
+            cell_count_kernel<3><<<grid_for(n, 256), 256, 0, st>>>(make_grid<3>(k), d_pts, n, cid, k->cell_start);
+        S3_HIP_CHECK_MEM(hipGetLastError());
+        S3_HIP_CHECK_MEM(exclusive_scan<int32_t>(k->cell_start, k->cell_start, nscan, scan_tmp, st));
+        if (dim == 2)
+            scatter_kernel<2><<<grid_for(n, 256), 256, 0, st>>>(d_pts, n, cid, k->cell_start, cursor, k->pts, k->orig);
+        else
+            scatter_kernel<3><<<grid_for(n, 256), 256, 0, st>>>(d_pts, n, cid, k->cell_start, cursor, k->pts, k->orig);
+        S3_HIP_CHECK_MEM(hipGetLastError());
+        S3_HIP_CHECK_MEM(hipStreamSynchronize(st));
+    }
     // ---- second level: buckets with more than 8x the target occupancy get their own sub-lattice, so that strongly graded
     //      point clouds (boundary-layer meshes) do not degenerate into scanning thousands of points per bucket --------
     {
         const int split = (int)std::ceil(8.0 * occ);
-        int32_t *sub_size = nullptr, *scan_tmp2 = nullptr, *sid = nullptr, *cur2 = nullptr, *orig2 = nullptr;
-        double *pts2 = nullptr;
-        unsigned long long *d_nref = nullptr;
-        auto fail2 = [&](int rc) {
-            for (void *q : {(void *)sub_size, (void *)scan_tmp2, (void *)sid, (void *)cur2, (void *)orig2, (void *)pts2, (void *)d_nref})
-                if (q) (void)hipFree(q);
-            s3_knn_destroy(k);
-            return rc;
-        };
-#define S3_TRY2(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            s3::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);  \
-            return fail2(_e == hipErrorOutOfMemory ? S3_ENOMEM : S3_EHIP);                             \
-        }                                                                                              \
-    } while (0)
+        DevBuf<int32_t> sub_size, scan_tmp2, sid, cur2, orig2;
+        DevBuf<double> pts2;
+        DevBuf<unsigned long long> d_nref;
         const int64_t nscan2 = ncell + 1;
-        S3_TRY2(hipMalloc(&k->sub_res, ncell));
-        S3_TRY2(hipMalloc(&sub_size, sizeof(int32_t) * nscan2));
-        S3_TRY2(hipMalloc(&scan_tmp2, sizeof(int32_t) * scan_tmp_items(nscan2)));
-        S3_TRY2(hipMalloc(&d_nref, sizeof(unsigned long long)));
-        S3_TRY2(hipMemsetAsync(d_nref, 0, sizeof(unsigned long long), st));
+        S3_HIP_CHECK_MEM(k->sub_res.alloc((size_t)ncell));
+        S3_HIP_CHECK_MEM(sub_size.alloc((size_t)nscan2));
+        S3_HIP_CHECK_MEM(scan_tmp2.alloc(scan_tmp_items(nscan2)));
+        S3_HIP_CHECK_MEM(d_nref.alloc(1));
+        S3_HIP_CHECK_MEM(hipMemsetAsync(d_nref, 0, sizeof(unsigned long long), st));
         sub_plan_kernel<<<grid_for(nscan2, 256), 256, 0, st>>>(k->cell_start, ncell, split, occ, dim, k->sub_res, sub_size, d_nref);
-        S3_TRY2(hipGetLastError());
-        S3_TRY2(exclusive_scan<int32_t>(sub_size, sub_size, nscan2, scan_tmp2, st));
+        S3_HIP_CHECK_MEM(hipGetLastError());
+        S3_HIP_CHECK_MEM(exclusive_scan<int32_t>(sub_size, sub_size, nscan2, scan_tmp2, st));
         unsigned long long nref = 0;
         int32_t pool = 0;
-        S3_TRY2(hipMemcpyAsync(&nref, d_nref, sizeof(nref), hipMemcpyDeviceToHost, st));
-        S3_TRY2(hipMemcpyAsync(&pool, sub_size + ncell, sizeof(pool), hipMemcpyDeviceToHost, st));
-        S3_TRY2(hipStreamSynchronize(st));
+        S3_HIP_CHECK_MEM(hipMemcpyAsync(&nref, d_nref, sizeof(nref), hipMemcpyDeviceToHost, st));
+        S3_HIP_CHECK_MEM(hipMemcpyAsync(&pool, sub_size + ncell, sizeof(pool), hipMemcpyDeviceToHost, st));
+        S3_HIP_CHECK_MEM(hipStreamSynchronize(st));
         k->n_refined = (int64_t)nref;
-        k->sub_off = sub_size;           // the scanned sizes are the table offsets
-        sub_size = nullptr;
+        k->sub_off = std::move(sub_size);           // the scanned sizes are the table offsets
         if (nref > 0) {
-            S3_TRY2(hipMalloc(&k->sub_start, sizeof(int32_t) * (size_t)pool));
-            S3_TRY2(hipMalloc(&cur2, sizeof(int32_t) * (size_t)pool));
-            S3_TRY2(hipMalloc(&sid, sizeof(int32_t) * n));
-            S3_TRY2(hipMalloc(&pts2, sizeof(double) * n * dim));
-            S3_TRY2(hipMalloc(&orig2, sizeof(int32_t) * n));
-            S3_TRY2(hipMemsetAsync(k->sub_start, 0, sizeof(int32_t) * (size_t)pool, st));
-            S3_TRY2(hipMemsetAsync(cur2, 0, sizeof(int32_t) * (size_t)pool, st));
+            S3_HIP_CHECK_MEM(k->sub_start.alloc((size_t)pool));
+            S3_HIP_CHECK_MEM(cur2.alloc((size_t)pool));
+            S3_HIP_CHECK_MEM(sid.alloc((size_t)n));
+            S3_HIP_CHECK_MEM(pts2.alloc((size_t)n * dim));
+            S3_HIP_CHECK_MEM(orig2.alloc((size_t)n));
+            S3_HIP_CHECK_MEM(hipMemsetAsync(k->sub_start, 0, sizeof(int32_t) * (size_t)pool, st));
+            S3_HIP_CHECK_MEM(hipMemsetAsync(cur2, 0, sizeof(int32_t) * (size_t)pool, st));
             if (dim == 2) {
                 sub_count_kernel<2><<<grid_for(n, 256), 256, 0, st>>>(make_grid<2>(k), k->pts, n, k->sub_res, k->sub_off, k->sub_start, sid);
                 sub_scan_kernel<<<(unsigned)ncell, 64, 0, st>>>(k->cell_start, k->sub_res, k->sub_off, k->sub_start, dim);
@@ -1667,30 +1637,17 @@ int s3_knn_create(const double *d_pts, int64_t n, int dim, double target_occupan
                 sub_scatter_kernel<3><<<grid_for(n, 256), 256, 0, st>>>(make_grid<3>(k), k->pts, k->orig, n, sid, k->sub_off,
                                                                        k->sub_start, cur2, pts2, orig2);
             }
-            S3_TRY2(hipGetLastError());
-            S3_TRY2(hipStreamSynchronize(st));
+            S3_HIP_CHECK_MEM(hipGetLastError());
+            S3_HIP_CHECK_MEM(hipStreamSynchronize(st));
             std::swap(k->pts, pts2);
             std::swap(k->orig, orig2);
         }
-        for (void *q : {(void *)scan_tmp2, (void *)sid, (void *)cur2, (void *)orig2, (void *)pts2, (void *)d_nref})
-            if (q) (void)hipFree(q);
-#undef S3_TRY2
     }
-    *out = k;
+    *out = owner.release();
     return S3_OK;
 }
 
-void s3_knn_destroy(s3_knn *knn) {
-    if (!knn) return;
-    if (knn->pts) (void)hipFree(knn->pts);
-    if (knn->orig) (void)hipFree(knn->orig);
-    if (knn->cell_start) (void)hipFree(knn->cell_start);
-    if (knn->y) (void)hipFree(knn->y);
-    if (knn->sub_res) (void)hipFree(knn->sub_res);
-    if (knn->sub_off) (void)hipFree(knn->sub_off);
-    if (knn->sub_start) (void)hipFree(knn->sub_start);
-    delete knn;
-}
+void s3_knn_destroy(s3_knn *knn) { delete knn; }
 
 int s3_knn_info(const s3_knn *knn, int64_t *h_n_buckets, int64_t *h_n_refined) {
     S3_REQUIRE(knn != nullptr, "s3_knn_info: null index");
@@ -1701,7 +1658,7 @@ int s3_knn_info(const s3_knn *knn, int64_t *h_n_buckets, int64_t *h_n_refined) {
 
 int s3_knn_set_values(s3_knn *knn, const double *d_y, s3_stream stream) {
     S3_REQUIRE(knn != nullptr && d_y != nullptr, "s3_knn_set_values: null argument");
-    if (!knn->y) S3_HIP_CHECK(hipMalloc(&knn->y, sizeof(double) * knn->n));
+    if (!knn->y) S3_HIP_CHECK(knn->y.alloc((size_t)knn->n));
     permute_values_kernel<<<grid_for(knn->n, 256), 256, 0, as_stream(stream)>>>(d_y, knn->orig, knn->n, knn->y);
     S3_LAUNCH_CHECK();
     return S3_OK;

@@ -1,19 +1,17 @@
 // Device-side plan construction (plan_build.hip), used by s3_interp_plan_create (interp_plan.hip).
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "common.h"
 
 namespace s3 {
 
-// device tables of a plan; every non-null pointer is a hipMalloc allocation owned by the caller (also after an error)
+// device tables of a plan (host only: no kernel takes the struct); whatever was allocated before an error goes with the struct
 struct PlanTables {
-    int32_t *perm = nullptr;             // [nc] processing position -> cell id
-    int32_t *tile_cell_begin = nullptr;  // [n_tiles+1]
-    int32_t *tile_row_begin = nullptr;   // [n_tiles+1]
-    int32_t *rows = nullptr;             // [total_rows] distinct source rows, tile after tile
-    uint16_t *loc = nullptr;             // [nc*k] per tile: [m][cell in tile] -> position in the tile's row list
+    DevBuf<int32_t> perm;             // [nc] processing position -> cell id
+    DevBuf<int32_t> tile_cell_begin;  // [n_tiles+1]
+    DevBuf<int32_t> tile_row_begin;   // [n_tiles+1]
+    DevBuf<int32_t> rows;             // [total_rows] distinct source rows, tile after tile
+    DevBuf<uint16_t> loc;             // [nc*k] per tile: [m][cell in tile] -> position in the tile's row list
     int64_t n_tiles = 0, total_rows = 0;
 };
 

@@ -222,35 +222,22 @@ gather_kernel(const int32_t *__restrict__ blk_rows, const int32_t *__restrict__ 
 
 }  // namespace
 
-struct Scratch {                           // frees whatever was allocated when it goes out of scope
-    std::vector<void *> ptrs;
-    ~Scratch() { for (void *p : ptrs) (void)hipFree(p); }
-    template <typename T> hipError_t alloc(T **p, size_t n) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(p), sizeof(T) * (n ? n : 1));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
+// what spatial_perm queues work on: the caller keeps it until the stream has been synchronised
+struct PermScratch {
+    DevBuf<double> part;
+    DevBuf<uint64_t> key_in, key_out;
+    DevBuf<int32_t> val_in, hist;
 };
 
-#define S3_PB_CHECK(expr)                                                                             \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) {                                                                       \
-            s3::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return _e == hipErrorOutOfMemory ? S3_ENOMEM : S3_EHIP;                                   \
-        }                                                                                             \
-    } while (0)
-
 // Hilbert-curve order of n points (dim 2 | 3): bounding box, 48-bit keys, stable radix sort -> perm[position] = point
-static int spatial_perm(const double *d_points, int64_t n, int dim, hipStream_t st, int32_t *d_perm, Scratch &tmp) {
+static int spatial_perm(const double *d_points, int64_t n, int dim, hipStream_t st, int32_t *d_perm, PermScratch &tmp) {
     const int nb = 256;
-    double *d_part = nullptr;
-    S3_PB_CHECK(tmp.alloc(&d_part, (size_t)nb * 6));
-    plan_bbox_kernel<<<nb, 256, 0, st>>>(d_points, n, dim, d_part);
-    S3_PB_CHECK(hipGetLastError());
+    S3_HIP_CHECK_MEM(tmp.part.alloc((size_t)nb * 6));
+    plan_bbox_kernel<<<nb, 256, 0, st>>>(d_points, n, dim, tmp.part);
+    S3_HIP_CHECK_MEM(hipGetLastError());
     std::vector<double> part((size_t)nb * 6);
-    S3_PB_CHECK(hipMemcpyAsync(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
-    S3_PB_CHECK(hipStreamSynchronize(st));
+    S3_HIP_CHECK_MEM(hipMemcpyAsync(part.data(), tmp.part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
+    S3_HIP_CHECK_MEM(hipStreamSynchronize(st));
     KeyParams kp{};
     double hi[3] = {-1e300, -1e300, -1e300};
     for (int j = 0; j < 3; ++j) kp.lo[j] = 1e300;
@@ -264,82 +251,79 @@ static int spatial_perm(const double *d_points, int64_t n, int dim, hipStream_t 
     kp.dim = dim;
     kp.bits = dim == 3 ? 16 : 24;                       // 48-bit keys
     kp.scale = ext > 0 && std::isfinite(ext) ? ((double)((1u << kp.bits) - 1) / ext) : 0.0;
-    uint64_t *key_in = nullptr, *key_out = nullptr;
-    int32_t *val_in = nullptr;
-    S3_PB_CHECK(tmp.alloc(&key_in, (size_t)n));
-    S3_PB_CHECK(tmp.alloc(&key_out, (size_t)n));
-    S3_PB_CHECK(tmp.alloc(&val_in, (size_t)n));
-    key_kernel<<<grid_for(n, 256), 256, 0, st>>>(d_points, n, kp, key_in, val_in);
-    S3_PB_CHECK(hipGetLastError());
+    S3_HIP_CHECK_MEM(tmp.key_in.alloc((size_t)n));
+    S3_HIP_CHECK_MEM(tmp.key_out.alloc((size_t)n));
+    S3_HIP_CHECK_MEM(tmp.val_in.alloc((size_t)n));
+    key_kernel<<<grid_for(n, 256), 256, 0, st>>>(d_points, n, kp, tmp.key_in, tmp.val_in);
+    S3_HIP_CHECK_MEM(hipGetLastError());
     // stable LSD radix sort of (key, position) pairs (csrc/scan_sort.h); 48-bit keys: six passes, the result ends in the
     // buffers it started from
-    int32_t *d_hist = nullptr;
     const size_t hist_items = sort_hist_items(n);
-    S3_PB_CHECK(tmp.alloc(&d_hist, hist_items + scan_tmp_items((int64_t)hist_items)));
+    S3_HIP_CHECK_MEM(tmp.hist.alloc(hist_items + scan_tmp_items((int64_t)hist_items)));
     bool in_alt = false;
-    S3_PB_CHECK(radix_sort_pairs(key_in, key_out, val_in, d_perm, n, dim * kp.bits, d_hist, st, &in_alt));
-    if (!in_alt) S3_PB_CHECK(hipMemcpyAsync(d_perm, val_in, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    S3_HIP_CHECK_MEM(radix_sort_pairs(tmp.key_in, tmp.key_out, tmp.val_in, d_perm, n, dim * kp.bits, tmp.hist, st, &in_alt));
+    if (!in_alt) S3_HIP_CHECK_MEM(hipMemcpyAsync(d_perm, tmp.val_in, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
     return S3_OK;
 }
 
 int build_plan_tables(const int32_t *d_idx, int64_t nc, int k, int64_t n_src, const double *d_centers, int dim, int tc,
                       int ucap, hipStream_t st, PlanTables *out) {
-    Scratch tmp;
     // ---- 1. validation + processing order ----------------------------------------------------------------------
-    int32_t *d_bad = nullptr;
-    S3_PB_CHECK(tmp.alloc(&d_bad, 1));
-    S3_PB_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int32_t), st));
+    DevBuf<int32_t> d_bad;
+    PermScratch tmp;
+    S3_HIP_CHECK_MEM(d_bad.alloc(1));
+    S3_HIP_CHECK_MEM(hipMemsetAsync(d_bad, 0, sizeof(int32_t), st));
     validate_kernel<<<grid_for(nc * k, 256), 256, 0, st>>>(d_idx, nc * k, (int32_t)n_src, d_bad);
-    S3_PB_CHECK(hipGetLastError());
+    S3_HIP_CHECK_MEM(hipGetLastError());
 
-    S3_PB_CHECK(hipMalloc(reinterpret_cast<void **>(&out->perm), sizeof(int32_t) * nc));
+    S3_HIP_CHECK_MEM(out->perm.alloc((size_t)nc));
     if (d_centers) {
         const int rc = spatial_perm(d_centers, nc, dim, st, out->perm, tmp);
         if (rc != S3_OK) return rc;
     } else {
         iota_kernel<<<grid_for(nc, 256), 256, 0, st>>>(out->perm, nc);
-        S3_PB_CHECK(hipGetLastError());
+        S3_HIP_CHECK_MEM(hipGetLastError());
     }
 
     // ---- 2. per-block greedy packing ---------------------------------------------------------------------------
     const int cb = BLOCK_TILES * tc;
     const int64_t n_blocks = (nc + cb - 1) / cb;
     S3_REQUIRE(n_blocks < ((int64_t)1 << 31), "s3_interp_plan_create: too many cells");
-    int32_t *blk_rows = nullptr, *blk_tiles = nullptr, *cnt_t = nullptr, *cnt_r = nullptr, *off_t = nullptr, *off_r = nullptr;
-    S3_PB_CHECK(tmp.alloc(&blk_rows, (size_t)n_blocks * cb * k));
-    S3_PB_CHECK(tmp.alloc(&blk_tiles, (size_t)n_blocks * cb * 2));
-    S3_PB_CHECK(tmp.alloc(&cnt_t, (size_t)n_blocks));
-    S3_PB_CHECK(tmp.alloc(&cnt_r, (size_t)n_blocks));
-    S3_PB_CHECK(tmp.alloc(&off_t, (size_t)n_blocks));
-    S3_PB_CHECK(tmp.alloc(&off_r, (size_t)n_blocks));
-    S3_PB_CHECK(hipMalloc(reinterpret_cast<void **>(&out->loc), sizeof(uint16_t) * (size_t)nc * k));
+    DevBuf<int32_t> blk_rows, blk_tiles, cnt_t, cnt_r, off_t, off_r;
+    S3_HIP_CHECK_MEM(blk_rows.alloc((size_t)n_blocks * cb * k));
+    S3_HIP_CHECK_MEM(blk_tiles.alloc((size_t)n_blocks * cb * 2));
+    S3_HIP_CHECK_MEM(cnt_t.alloc((size_t)n_blocks));
+    S3_HIP_CHECK_MEM(cnt_r.alloc((size_t)n_blocks));
+    S3_HIP_CHECK_MEM(off_t.alloc((size_t)n_blocks));
+    S3_HIP_CHECK_MEM(off_r.alloc((size_t)n_blocks));
+    S3_HIP_CHECK_MEM(out->loc.alloc((size_t)nc * k));
     const size_t lds = sizeof(int32_t) * HT_SLOTS + sizeof(uint16_t) * HT_SLOTS + sizeof(uint16_t) * (size_t)tc * k;
     pack_kernel<<<(unsigned)n_blocks, 64, lds, st>>>(d_idx, out->perm, nc, k, tc, cb, ucap, blk_rows, blk_tiles, cnt_t, cnt_r,
                                                      out->loc);
-    S3_PB_CHECK(hipGetLastError());
+    S3_HIP_CHECK_MEM(hipGetLastError());
 
     // ---- 3. offsets + compact tables ---------------------------------------------------------------------------
-    int32_t *d_scan = nullptr;
-    S3_PB_CHECK(tmp.alloc(&d_scan, scan_tmp_items(n_blocks)));
-    S3_PB_CHECK(exclusive_scan<int32_t>(cnt_t, off_t, n_blocks, d_scan, st));
-    S3_PB_CHECK(exclusive_scan<int32_t>(cnt_r, off_r, n_blocks, d_scan, st));
+    DevBuf<int32_t> d_scan;
+    S3_HIP_CHECK_MEM(d_scan.alloc(scan_tmp_items(n_blocks)));
+    S3_HIP_CHECK_MEM(exclusive_scan<int32_t>(cnt_t, off_t, n_blocks, d_scan, st));
+    S3_HIP_CHECK_MEM(exclusive_scan<int32_t>(cnt_r, off_r, n_blocks, d_scan, st));
     int32_t last[4] = {0, 0, 0, 0}, bad = 0;                      // offsets and counts of the last block -> totals
-    S3_PB_CHECK(hipMemcpyAsync(&last[0], off_t + n_blocks - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    S3_PB_CHECK(hipMemcpyAsync(&last[1], off_r + n_blocks - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    S3_PB_CHECK(hipMemcpyAsync(&last[2], cnt_t + n_blocks - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    S3_PB_CHECK(hipMemcpyAsync(&last[3], cnt_r + n_blocks - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    S3_PB_CHECK(hipMemcpyAsync(&bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    S3_PB_CHECK(hipStreamSynchronize(st));
+    S3_HIP_CHECK_MEM(hipMemcpyAsync(&last[0], off_t + n_blocks - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    S3_HIP_CHECK_MEM(hipMemcpyAsync(&last[1], off_r + n_blocks - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    S3_HIP_CHECK_MEM(hipMemcpyAsync(&last[2], cnt_t + n_blocks - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    S3_HIP_CHECK_MEM(hipMemcpyAsync(&last[3], cnt_r + n_blocks - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    S3_HIP_CHECK_MEM(hipMemcpyAsync(&bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    S3_HIP_CHECK_MEM(hipStreamSynchronize(st));
     S3_REQUIRE(bad == 0, "s3_interp_plan_create: neighbour index outside [0, %lld) in the table", (long long)n_src);
     out->n_tiles = (int64_t)last[0] + last[2];
     out->total_rows = (int64_t)last[1] + last[3];
-    S3_PB_CHECK(hipMalloc(reinterpret_cast<void **>(&out->tile_cell_begin), sizeof(int32_t) * (size_t)(out->n_tiles + 1)));
-    S3_PB_CHECK(hipMalloc(reinterpret_cast<void **>(&out->tile_row_begin), sizeof(int32_t) * (size_t)(out->n_tiles + 1)));
-    S3_PB_CHECK(hipMalloc(reinterpret_cast<void **>(&out->rows), sizeof(int32_t) * (size_t)std::max<int64_t>(out->total_rows, 1)));
+    S3_HIP_CHECK_MEM(out->tile_cell_begin.alloc((size_t)(out->n_tiles + 1)));
+    S3_HIP_CHECK_MEM(out->tile_row_begin.alloc((size_t)(out->n_tiles + 1)));
+    S3_HIP_CHECK_MEM(out->rows.alloc((size_t)out->total_rows));
     gather_kernel<<<(unsigned)n_blocks, 64, 0, st>>>(blk_rows, blk_tiles, cnt_t, cnt_r, off_t, off_r, cb, k, n_blocks,
                                                      out->tile_cell_begin, out->tile_row_begin, out->rows);
-    S3_PB_CHECK(hipGetLastError());
-    S3_PB_CHECK(hipStreamSynchronize(st));
+    S3_HIP_CHECK_MEM(hipGetLastError());
+    S3_HIP_CHECK_MEM(hipStreamSynchronize(st));
     return S3_OK;
 }
 
@@ -426,9 +410,9 @@ int s3_mark_rows(const int32_t *d_idx, int64_t n, int64_t n_src, int32_t *d_flag
     if (n == 0) return S3_OK;
     S3_REQUIRE(d_idx && d_flag, "s3_mark_rows: null array");
     hipStream_t st = s3::as_stream(stream);
-    s3::Scratch tmp;
-    int32_t *d_bad = nullptr, bad = 0;
-    S3_HIP_CHECK(tmp.alloc(&d_bad, 1));
+    s3::DevBuf<int32_t> d_bad;
+    int32_t bad = 0;
+    S3_HIP_CHECK(d_bad.alloc(1));
     S3_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int32_t), st));
     mark_rows_kernel<<<s3::grid_for(n, 256), 256, 0, st>>>(d_idx, n, (int32_t)n_src, d_flag, d_bad);
     S3_LAUNCH_CHECK();
@@ -441,11 +425,9 @@ int s3_mark_rows(const int32_t *d_idx, int64_t n, int64_t n_src, int32_t *d_flag
 int s3_compact_rows(int32_t *d_flag_remap, int64_t n_src, int32_t *d_used, int64_t *h_n_used, s3_stream stream) {
     S3_REQUIRE(n_src >= 1 && n_src < ((int64_t)1 << 31) && d_flag_remap && d_used && h_n_used, "s3_compact_rows: bad arguments");
     hipStream_t st = s3::as_stream(stream);
-    s3::Scratch tmp;
-    int32_t *pos = nullptr;
-    S3_HIP_CHECK(tmp.alloc(&pos, (size_t)n_src));
-    int32_t *d_scan = nullptr;
-    S3_HIP_CHECK(tmp.alloc(&d_scan, s3::scan_tmp_items(n_src)));
+    s3::DevBuf<int32_t> pos, d_scan;
+    S3_HIP_CHECK(pos.alloc((size_t)n_src));
+    S3_HIP_CHECK(d_scan.alloc(s3::scan_tmp_items(n_src)));
     S3_HIP_CHECK(s3::exclusive_scan<int32_t>(d_flag_remap, pos, n_src, d_scan, st));
     int32_t last_pos = 0, last_flag = 0;
     S3_HIP_CHECK(hipMemcpyAsync(&last_pos, pos + n_src - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -462,9 +444,9 @@ int s3_remap_indices(int32_t *d_idx, int64_t n, const int32_t *d_remap, int64_t 
     if (n == 0) return S3_OK;
     S3_REQUIRE(d_idx && d_remap, "s3_remap_indices: null array");
     hipStream_t st = s3::as_stream(stream);
-    s3::Scratch tmp;
-    int32_t *d_bad = nullptr, bad = 0;
-    S3_HIP_CHECK(tmp.alloc(&d_bad, 1));
+    s3::DevBuf<int32_t> d_bad;
+    int32_t bad = 0;
+    S3_HIP_CHECK(d_bad.alloc(1));
     S3_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int32_t), st));
     remap_kernel<<<s3::grid_for(n, 256), 256, 0, st>>>(d_idx, n, d_remap, (int32_t)n_src, d_bad);
     S3_LAUNCH_CHECK();
@@ -486,9 +468,9 @@ int s3_gather_rows(const void *d_src, int64_t n_src_rows, int64_t row_bytes, int
     S3_REQUIRE(d_ids != nullptr || n <= n_src_rows, "s3_gather_rows: more rows requested than the source holds");
     hipStream_t st = s3::as_stream(stream);
     if (d_ids) {
-        s3::Scratch tmp;
-        int32_t *d_bad = nullptr, bad = 0;
-        S3_HIP_CHECK(tmp.alloc(&d_bad, 1));
+        s3::DevBuf<int32_t> d_bad;
+        int32_t bad = 0;
+        S3_HIP_CHECK(d_bad.alloc(1));
         S3_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int32_t), st));
         check_ids_kernel<<<s3::grid_for(n, 256), 256, 0, st>>>(d_ids, n, (int32_t)n_src_rows, d_bad);
         S3_LAUNCH_CHECK();
@@ -540,9 +522,9 @@ __global__ void scatter_positions_kernel(const int32_t *__restrict__ ids, int64_
 int s3_positions_of(const int32_t *d_ids, int64_t n, int32_t *d_remap, int64_t n_src, s3_stream stream) {
     S3_REQUIRE(d_remap && n >= 0 && n_src >= 1 && n_src < ((int64_t)1 << 31) && (n == 0 || d_ids), "s3_positions_of: bad arguments");
     hipStream_t st = s3::as_stream(stream);
-    s3::Scratch tmp;
-    int32_t *d_bad = nullptr, bad = 0;
-    S3_HIP_CHECK(tmp.alloc(&d_bad, 1));
+    s3::DevBuf<int32_t> d_bad;
+    int32_t bad = 0;
+    S3_HIP_CHECK(d_bad.alloc(1));
     S3_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int32_t), st));
     fill_i32_kernel<<<s3::grid_for(n_src, 256), 256, 0, st>>>(d_remap, n_src, -1);
     if (n > 0) scatter_positions_kernel<<<s3::grid_for(n, 256), 256, 0, st>>>(d_ids, n, (int32_t)n_src, d_remap, d_bad);
@@ -555,7 +537,7 @@ int s3_positions_of(const int32_t *d_ids, int64_t n, int32_t *d_remap, int64_t n
 
 int s3_spatial_order(const double *d_points, int64_t n, int dim, int32_t *d_perm, s3_stream stream) {
     S3_REQUIRE(d_points && d_perm && n >= 1 && n < ((int64_t)1 << 31) && (dim == 2 || dim == 3), "s3_spatial_order: bad arguments");
-    s3::Scratch tmp;
+    s3::PermScratch tmp;
     const int rc = s3::spatial_perm(d_points, n, dim, s3::as_stream(stream), d_perm, tmp);
     if (rc != S3_OK) return rc;
     S3_HIP_CHECK(hipStreamSynchronize(s3::as_stream(stream)));       // the scratch arrays go away with `tmp`
@@ -567,17 +549,16 @@ int s3_exclusive_scan(const void *d_in, void *d_out, int64_t n, int elem_bytes, 
     S3_REQUIRE(n >= 0 && (n == 0 || (d_in && d_out)) && (elem_bytes == 4 || elem_bytes == 8), "s3_exclusive_scan: int32 / int64 arrays");
     if (n == 0) return S3_OK;
     hipStream_t st = s3::as_stream(stream);
-    s3::Scratch tmp;
+    s3::DevBuf<int32_t> t32;
+    s3::DevBuf<int64_t> t64;
     if (elem_bytes == 4) {
-        int32_t *t = nullptr;
-        S3_HIP_CHECK(tmp.alloc(&t, s3::scan_tmp_items(n)));
-        S3_HIP_CHECK(s3::exclusive_scan<int32_t>(static_cast<const int32_t *>(d_in), static_cast<int32_t *>(d_out), n, t, st));
+        S3_HIP_CHECK(t32.alloc(s3::scan_tmp_items(n)));
+        S3_HIP_CHECK(s3::exclusive_scan<int32_t>(static_cast<const int32_t *>(d_in), static_cast<int32_t *>(d_out), n, t32, st));
     } else {
-        int64_t *t = nullptr;
-        S3_HIP_CHECK(tmp.alloc(&t, s3::scan_tmp_items(n)));
-        S3_HIP_CHECK(s3::exclusive_scan<int64_t>(static_cast<const int64_t *>(d_in), static_cast<int64_t *>(d_out), n, t, st));
+        S3_HIP_CHECK(t64.alloc(s3::scan_tmp_items(n)));
+        S3_HIP_CHECK(s3::exclusive_scan<int64_t>(static_cast<const int64_t *>(d_in), static_cast<int64_t *>(d_out), n, t64, st));
     }
-    S3_HIP_CHECK(hipStreamSynchronize(st));                           // the scratch array goes away with `tmp`
+    S3_HIP_CHECK(hipStreamSynchronize(st));                           // the scratch array goes away after it
     return S3_OK;
 }
 
@@ -585,13 +566,12 @@ int s3_sort_pairs(uint64_t *d_keys, int32_t *d_vals, int64_t n, int bits, s3_str
     S3_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || (d_keys && d_vals)) && bits >= 1 && bits <= 64, "s3_sort_pairs: bad arguments");
     if (n == 0) return S3_OK;
     hipStream_t st = s3::as_stream(stream);
-    s3::Scratch tmp;
-    uint64_t *k2 = nullptr;
-    int32_t *v2 = nullptr, *hist = nullptr;
+    s3::DevBuf<uint64_t> k2;
+    s3::DevBuf<int32_t> v2, hist;
     const size_t items = s3::sort_hist_items(n);
-    S3_HIP_CHECK(tmp.alloc(&k2, (size_t)n));
-    S3_HIP_CHECK(tmp.alloc(&v2, (size_t)n));
-    S3_HIP_CHECK(tmp.alloc(&hist, items + s3::scan_tmp_items((int64_t)items)));
+    S3_HIP_CHECK(k2.alloc((size_t)n));
+    S3_HIP_CHECK(v2.alloc((size_t)n));
+    S3_HIP_CHECK(hist.alloc(items + s3::scan_tmp_items((int64_t)items)));
     bool in_alt = false;
     S3_HIP_CHECK(s3::radix_sort_pairs(d_keys, k2, d_vals, v2, n, bits, hist, st, &in_alt));
     if (in_alt) {

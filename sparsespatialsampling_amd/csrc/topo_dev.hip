@@ -34,6 +34,7 @@
 #include <algorithm>
 #include <cstring>
 #include <exception>
+#include <memory>
 #include <vector>
 
 using s3topo::INVALID;
@@ -57,7 +58,7 @@ struct s3_topo : TopoView {
     // scratch, grown on demand
     int64_t *ids = nullptr, *cnt = nullptr, *base = nullptr;
     int64_t ids_cap = 0;
-    void *scan_tmp = nullptr;
+    s3::DevBuf<int64_t> scan_tmp;
     size_t scan_tmp_bytes = 0;
     int32_t *rows_tmp = nullptr;
     int64_t rows_tmp_cap = 0;
@@ -78,6 +79,22 @@ struct s3_topo : TopoView {
     // tables replaced by larger ones: released at the next sync (hipFree waits for the whole device, i.e. for the KNN
     // kernel of the refine loop that runs beside the engine)
     std::vector<void *> retired;
+
+    // the view's tables stay raw pointers (the kernels take the view by value), as does what grow() manages: freed here
+    ~s3_topo() {
+        if (st) (void)hipStreamSynchronize(st);
+        void *ptrs[] = {level, parent, first_child, batch_pos, nb, node_idx, center, nodes, counters, ids, cnt,
+                        base, rows_tmp, flags, map, leaf_row, d_nb_table, d_rules, d_widths};
+        for (void *p : ptrs)
+            if (p) (void)hipFree(p);
+        scan_tmp.reset();
+        for (void *p : retired) (void)hipFree(p);
+        for (int b = 0; b < 2; ++b) {
+            if (h_stage[b]) (void)hipHostFree(h_stage[b]);
+            if (h_stage_free[b]) (void)hipEventDestroy(h_stage_free[b]);
+        }
+        if (st) (void)hipStreamDestroy(st);
+    }
 };
 
 namespace s3 {
@@ -338,10 +355,9 @@ template <typename T>
 static int grow(T *&p, int64_t &cap, int64_t want, int64_t keep, hipStream_t st, std::vector<void *> *retired = nullptr) {
     if (want <= cap) return S3_OK;
     const int64_t nc = std::max<int64_t>(std::max(want, cap * 2), 1024);
-    T *q = nullptr;
-    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&q), sizeof(T) * (size_t)nc);
-    if (e != hipSuccess) {
-        s3::set_error("topology engine: hipMalloc of %zu bytes failed: %s", sizeof(T) * (size_t)nc, hipGetErrorString(e));
+    DevBuf<T> q;                                         // given to the table only once the copy is queued
+    if (const int e = q.alloc((size_t)nc)) {
+        s3::set_error("topology engine: hipMalloc of %zu bytes failed: %s", sizeof(T) * (size_t)nc, hipGetErrorString((hipError_t)e));
         return S3_ENOMEM;
     }
     if (p && keep > 0) S3_HIP_CHECK(hipMemcpyAsync(q, p, sizeof(T) * (size_t)keep, hipMemcpyDeviceToDevice, st));
@@ -353,7 +369,7 @@ static int grow(T *&p, int64_t &cap, int64_t want, int64_t keep, hipStream_t st,
             (void)hipFree(p);
         }
     }
-    p = q;
+    p = q.release();
     cap = nc;
     return S3_OK;
 }
@@ -420,15 +436,12 @@ static int upload_ids(s3_topo *t, const int64_t *h_ids, int64_t n) {
 static int exclusive_scan(s3_topo *t, const int64_t *in, int64_t *out, int64_t n) {
     const size_t need = sizeof(int64_t) * scan_tmp_items(n);
     if (need > t->scan_tmp_bytes) {
-        if (t->scan_tmp) {
-            S3_HIP_CHECK(hipStreamSynchronize(t->st));
-            (void)hipFree(t->scan_tmp);
-            t->scan_tmp = nullptr;
-        }
-        S3_HIP_CHECK(hipMalloc(&t->scan_tmp, need));
+        if (t->scan_tmp) S3_HIP_CHECK(hipStreamSynchronize(t->st));       // queued scans still use the old one
+        t->scan_tmp_bytes = 0;
+        S3_HIP_CHECK(t->scan_tmp.alloc(scan_tmp_items(n)));
         t->scan_tmp_bytes = need;
     }
-    S3_HIP_CHECK(s3::exclusive_scan<int64_t>(in, out, n, static_cast<int64_t *>(t->scan_tmp), t->st));   // csrc/scan_sort.h
+    S3_HIP_CHECK(s3::exclusive_scan<int64_t>(in, out, n, t->scan_tmp, t->st));   // csrc/scan_sort.h
     return S3_OK;
 }
 
@@ -438,68 +451,42 @@ using namespace s3;
 
 extern "C" {
 
-void s3_topo_destroy(s3_topo *t) {
-    if (!t) return;
-    if (t->st) (void)hipStreamSynchronize(t->st);
-    void *ptrs[] = {t->level, t->parent, t->first_child, t->batch_pos, t->nb, t->node_idx, t->center, t->nodes, t->counters,
-                    t->ids, t->cnt, t->base, t->scan_tmp, t->rows_tmp, t->flags, t->map, t->leaf_row, t->d_nb_table,
-                    t->d_rules, t->d_widths};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (void *p : t->retired) (void)hipFree(p);
-    for (int b = 0; b < 2; ++b) {
-        if (t->h_stage[b]) (void)hipHostFree(t->h_stage[b]);
-        if (t->h_stage_free[b]) (void)hipEventDestroy(t->h_stage_free[b]);
-    }
-    if (t->st) (void)hipStreamDestroy(t->st);
-    delete t;
-}
+void s3_topo_destroy(s3_topo *t) { delete t; }
 
 int s3_topo_create(int dim, double width, const double *h_root_center, s3_topo **out) try {
     S3_REQUIRE(out != nullptr && h_root_center != nullptr, "s3_topo_create: null argument");
     *out = nullptr;
     S3_REQUIRE(dim == 2 || dim == 3, "s3_topo_create: dim must be 2 or 3, got %d", dim);
-    s3_topo *t = new s3_topo();
+    std::unique_ptr<s3_topo> owner(new s3_topo());
+    s3_topo *t = owner.get();
     *static_cast<TopoView *>(t) = TopoView{};
     t->dim = dim;
     t->nch = 1 << dim;
     t->nnb = dim == 2 ? 8 : 26;
     t->n_rules = dim == 2 ? s3topo::N_RULES_2D : s3topo::N_RULES_3D;
     t->width = width;
-    auto fail = [&](int rc) {
-        s3_topo_destroy(t);
-        return rc;
-    };
-#define S3_TOPO_TRY(EXPR)                                                                              \
-    do {                                                                                               \
-        const hipError_t e_ = (EXPR);                                                                  \
-        if (e_ != hipSuccess) {                                                                        \
-            s3::set_error("s3_topo_create: %s failed: %s", #EXPR, hipGetErrorString(e_));              \
-            return fail(e_ == hipErrorOutOfMemory ? S3_ENOMEM : S3_EHIP);                              \
-        }                                                                                              \
-    } while (0)
-    S3_TOPO_TRY(hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking));
+    S3_HIP_CHECK_MEM(hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking));
     NbEntry tab[8 * 26];
     s3topo::build_nb_table(dim, tab);
     const size_t tab_bytes = sizeof(NbEntry) * (size_t)t->nch * t->nnb;
-    S3_TOPO_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_nb_table), tab_bytes));
-    S3_TOPO_TRY(hipMemcpy(t->d_nb_table, tab, tab_bytes, hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMalloc(reinterpret_cast<void **>(&t->d_nb_table), tab_bytes));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->d_nb_table, tab, tab_bytes, hipMemcpyHostToDevice));
     const size_t rule_bytes = sizeof(NodeRule) * (size_t)t->nch * t->n_rules;
-    S3_TOPO_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_rules), rule_bytes));
-    S3_TOPO_TRY(hipMemcpy(t->d_rules, dim == 2 ? (const void *)s3topo::NODE_RULES_2D : (const void *)s3topo::NODE_RULES_3D, rule_bytes, hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMalloc(reinterpret_cast<void **>(&t->d_rules), rule_bytes));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->d_rules, dim == 2 ? (const void *)s3topo::NODE_RULES_2D : (const void *)s3topo::NODE_RULES_3D, rule_bytes, hipMemcpyHostToDevice));
     double widths[128];
     s3topo::fill_level_widths(width, widths, widths + 64);
-    S3_TOPO_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_widths), sizeof(widths)));
-    S3_TOPO_TRY(hipMemcpy(t->d_widths, widths, sizeof(widths), hipMemcpyHostToDevice));
-    S3_TOPO_TRY(hipMalloc(reinterpret_cast<void **>(&t->counters), 8 * sizeof(int64_t)));
+    S3_HIP_CHECK_MEM(hipMalloc(reinterpret_cast<void **>(&t->d_widths), sizeof(widths)));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->d_widths, widths, sizeof(widths), hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMalloc(reinterpret_cast<void **>(&t->counters), 8 * sizeof(int64_t)));
     t->nb_table = t->d_nb_table;
     t->rules = t->d_rules;
     t->half_width = t->d_widths;
     t->quarter_width = t->d_widths + 64;
     int rc = reserve_cells(t, 1);
-    if (rc != S3_OK) return fail(rc);
+    if (rc != S3_OK) return rc;
     rc = grow<double>(t->nodes, t->node_cap, (int64_t)t->nch * dim * 1024, 0, t->st);
-    if (rc != S3_OK) return fail(rc);
+    if (rc != S3_OK) return rc;
     t->node_cap /= dim;
     // root cell and its nodes (s_cube.py:368, 386-394: centre + dir * 0.5 * width, ids 0..2^d-1)
     std::vector<int32_t> nbrow(t->nnb, -1);
@@ -511,19 +498,18 @@ int s3_topo_create(int dim, double width, const double *h_root_center, s3_topo *
     }
     const int32_t zero = 0, minus1 = -1, leaf = LEAF;
     const int64_t counters[8] = {t->nch, 0, INT64_MAX, -1, 0, 0, 0, 0};
-    S3_TOPO_TRY(hipMemcpy(t->level, &zero, 4, hipMemcpyHostToDevice));
-    S3_TOPO_TRY(hipMemcpy(t->parent, &minus1, 4, hipMemcpyHostToDevice));
-    S3_TOPO_TRY(hipMemcpy(t->first_child, &leaf, 4, hipMemcpyHostToDevice));
-    S3_TOPO_TRY(hipMemcpy(t->batch_pos, &minus1, 4, hipMemcpyHostToDevice));
-    S3_TOPO_TRY(hipMemcpy(t->nb, nbrow.data(), 4 * (size_t)t->nnb, hipMemcpyHostToDevice));
-    S3_TOPO_TRY(hipMemcpy(t->node_idx, ni.data(), 8 * (size_t)t->nch, hipMemcpyHostToDevice));
-    S3_TOPO_TRY(hipMemcpy(t->center, h_root_center, 8 * (size_t)dim, hipMemcpyHostToDevice));
-    S3_TOPO_TRY(hipMemcpy(t->nodes, nodes.data(), 8 * nodes.size(), hipMemcpyHostToDevice));
-    S3_TOPO_TRY(hipMemcpy(t->counters, counters, sizeof(counters), hipMemcpyHostToDevice));
-#undef S3_TOPO_TRY
+    S3_HIP_CHECK_MEM(hipMemcpy(t->level, &zero, 4, hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->parent, &minus1, 4, hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->first_child, &leaf, 4, hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->batch_pos, &minus1, 4, hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->nb, nbrow.data(), 4 * (size_t)t->nnb, hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->node_idx, ni.data(), 8 * (size_t)t->nch, hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->center, h_root_center, 8 * (size_t)dim, hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->nodes, nodes.data(), 8 * nodes.size(), hipMemcpyHostToDevice));
+    S3_HIP_CHECK_MEM(hipMemcpy(t->counters, counters, sizeof(counters), hipMemcpyHostToDevice));
     t->n_used = 1;
     t->n_nodes_bound = t->nch;
-    *out = t;
+    *out = owner.release();
     return S3_OK;
 } catch (const std::exception &e) {
     s3::set_error("s3_topo_create: %s", e.what());
@@ -645,44 +631,43 @@ int s3_topo_finalize(s3_topo *t, int64_t *h_n_leaf, int64_t *h_n_unique_nodes) {
     if (rc != S3_OK) return rc;
     t->leaf_row_cap = c0;
     t->map_cap = c1;
-    int64_t *flag = nullptr, *scan = nullptr;               // temporaries of this call
-    S3_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&flag), sizeof(int64_t) * (size_t)m));
-    if (hipMalloc(reinterpret_cast<void **>(&scan), sizeof(int64_t) * (size_t)m) != hipSuccess) {
-        (void)hipFree(flag);
+    DevBuf<int64_t> flag, scan;                             // temporaries of this call
+    S3_HIP_CHECK(flag.alloc((size_t)m));
+    if (scan.alloc((size_t)m) != 0) {
         s3::set_error("s3_topo_finalize: out of device memory");
         return S3_ENOMEM;
     }
-    auto done = [&](int code) {
-        (void)hipStreamSynchronize(t->st);
-        (void)hipFree(flag);
-        (void)hipFree(scan);
-        return code;
-    };
+    // declared after the two, so it runs before they are freed on every way out: the engine's stream is non-blocking and what
+    // is queued on it still reads them
+    struct SyncOnExit {
+        hipStream_t st;
+        ~SyncOnExit() { (void)hipStreamSynchronize(st); }
+    } sync_first{t->st};
     const int64_t reset[2] = {INT64_MAX, -1};
     if (hipMemcpyAsync(t->counters + 2, reset, sizeof(reset), hipMemcpyHostToDevice, t->st) != hipSuccess ||
         hipMemsetAsync(t->flags, 0, (size_t)nn, t->st) != hipSuccess)
-        return done(S3_EHIP);
+        return S3_EHIP;
     const TopoView v = *t;
     topo_mark_used_kernel<<<blocks_for(nc), TB, 0, t->st>>>(v, nc, flag, t->flags);
     rc = exclusive_scan(t, flag, t->leaf_row, nc);
-    if (rc != S3_OK) return done(rc);
+    if (rc != S3_OK) return rc;
     int64_t last[2] = {0, 0}, lastk[2] = {0, 0};
     if (hipMemcpyAsync(&last[0], flag + (nc - 1), 8, hipMemcpyDeviceToHost, t->st) != hipSuccess ||
         hipMemcpyAsync(&last[1], t->leaf_row + (nc - 1), 8, hipMemcpyDeviceToHost, t->st) != hipSuccess)
-        return done(S3_EHIP);
+        return S3_EHIP;
     topo_keep_kernel<<<blocks_for(nn), TB, 0, t->st>>>(v, nn, t->flags, flag);
     rc = exclusive_scan(t, flag, scan, nn);
-    if (rc != S3_OK) return done(rc);
+    if (rc != S3_OK) return rc;
     topo_map_kernel<<<blocks_for(nn), TB, 0, t->st>>>(nn, t->flags, scan, flag, t->map);
     if (hipMemcpyAsync(&lastk[0], flag + (nn - 1), 8, hipMemcpyDeviceToHost, t->st) != hipSuccess ||
         hipMemcpyAsync(&lastk[1], scan + (nn - 1), 8, hipMemcpyDeviceToHost, t->st) != hipSuccess)
-        return done(S3_EHIP);
-    if (hipStreamSynchronize(t->st) != hipSuccess || hipGetLastError() != hipSuccess) return done(S3_EHIP);
+        return S3_EHIP;
+    if (hipStreamSynchronize(t->st) != hipSuccess || hipGetLastError() != hipSuccess) return S3_EHIP;
     t->n_leaf = last[0] + last[1];
     t->n_unique = lastk[0] + lastk[1];
     *h_n_leaf = t->n_leaf;
     *h_n_unique_nodes = t->n_unique;
-    return done(S3_OK);
+    return S3_OK;
 }
 
 // the assembled grid after s3_topo_finalize, into device arrays of the caller: faces [n_leaf][2^d] (int32 when as32, else

@@ -1,5 +1,5 @@
 """CPU-side sanitizer job (no GPU sanitizer exists on the pool): the host-side native code -- the transfer lanes of libs3hip.so
-(csrc/host_lanes.h), the topology engine + CPython-set restatement (libs3topo.so) and the HDF5 sink (libs3h5.so) -- built with
+(csrc/host_lanes.h), its owner of device allocations (csrc/dev_buf.h), the topology engine + CPython-set restatement (libs3topo.so) and the HDF5 sink (libs3h5.so) -- built with
 -fsanitize=thread / address,undefined and driven by their own tests."""
 import os
 import subprocess
@@ -30,6 +30,18 @@ def test_transfer_lanes_under_sanitizers(tmp_path, flags, env):
                     "-lpthread"], check=True)
     run = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
     assert run.returncode == 0 and "lanes_test ok" in run.stdout, run.stdout[-2000:] + run.stderr[-4000:]
+
+
+def test_device_buffer_owner_under_asan_ubsan(tmp_path):
+    """DevBuf (csrc/dev_buf.h), the one owner of device allocations in libs3hip.so, over a counting host allocator: every way a
+    buffer can change hands or go out of scope ends with zero outstanding blocks (tests/native/dev_buf_test.cpp)"""
+    _runtime("libasan.so")
+    exe = str(tmp_path / "dev_buf_test")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
+                    os.path.join(ROOT, "tests", "native", "dev_buf_test.cpp"), "-o", exe], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120,
+                         env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    assert run.returncode == 0 and run.stdout.strip().splitlines()[-1].startswith("dev_buf_test ok"), run.stdout[-2000:] + run.stderr[-4000:]
 
 
 def test_topology_engine_and_hdf5_sink_under_asan_ubsan(tmp_path):

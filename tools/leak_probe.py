@@ -1,4 +1,5 @@
-"""dev helper: device-memory leak check -- handles created and destroyed in a loop must not grow the memory in use"""
+"""dev helper: device-memory leak check -- handles created and destroyed in a loop must not grow the memory in use
+(the suite's form of this check, per handle and with refused calls: tests/test_gpu_handles_release.py)"""
 import os, sys
 import numpy as np, torch as pt
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
