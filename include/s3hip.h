@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 11
+#define S3_ABI_VERSION 12
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -474,6 +474,25 @@ int s3_gram(const void *d_x, int dtype, int64_t n_rows, int64_t t, int64_t in_st
             const double *d_weight /*[n_rows] or NULL*/, double *d_gram /*[t,t]*/, void *d_scratch, s3_stream stream);
 int s3_tall_gemm(const void *d_l, int dtype, int64_t m, int64_t k, int64_t l_stride, const double *d_b /*[k,n]*/, int64_t n,
                  double *d_c /*[m,n]*/, s3_stream stream);
+
+/* Windowed DFT of the overlapping segments of every row, on the same matrix cores -- the step behind Welch spectra and spectral POD
+ * (sparsespatialsampling_amd/spectral.py; the reference's post_processing/compare_svd_OAT.py:56-70 calls scipy.signal.welch).  Row i,
+ * segment b (samples b * hop ... b * hop + nperseg - 1), frequency column f:
+ *   c[i,b,f] = sum_l (x[i, b * hop + l] - mean[i]) (bre[l,f] + i bim[l,f])
+ * d_x [n_rows][t] f32 or f64 (dtype: S3_DTYPE_*), read where it lies, row pitch in_stride ELEMENTS (f32 load width chosen per launch
+ * from (pointer | in_stride * 4 | hop * 4) & 15); d_mean [n_rows] or NULL; d_bre / d_bim [nperseg][n_f] f64 contiguous: window,
+ * detrend and twiddles of the caller's choice (any nperseg: a direct DFT).  Needs (n_blk - 1) * hop + nperseg <= t <= in_stride;
+ * samples past the last segment are not read.
+ *   s3_segment_dft: d_coef [n_rows][n_f][n_blk][2] f64 contiguous (Re, Im).  Frequency f's matrix is the pitched real
+ *                   [n_rows][2 n_blk] matrix at d_coef + f * 2 * n_blk with row pitch n_f * n_blk * 2: s3_gram / s3_tall_gemm take it.
+ *   s3_segment_psd: d_psd [n_rows][n_f] = d_scale[f] * sum_b |c[i,b,f]|^2, summed in registers in segment order and written once:
+ *                   nothing of size n_rows * n_blk * n_f exists, no atomics, the same bits in every run. */
+int s3_segment_dft(const void *d_x, int dtype, int64_t n_rows, int64_t t, int64_t in_stride, const double *d_mean /*[n_rows] or NULL*/,
+                   int64_t nperseg, int64_t hop, int64_t n_blk, const double *d_bre, const double *d_bim, int64_t n_f,
+                   double *d_coef /*[n_rows][n_f][n_blk][2]*/, s3_stream stream);
+int s3_segment_psd(const void *d_x, int dtype, int64_t n_rows, int64_t t, int64_t in_stride, const double *d_mean /*[n_rows] or NULL*/,
+                   int64_t nperseg, int64_t hop, int64_t n_blk, const double *d_bre, const double *d_bim, int64_t n_f,
+                   const double *d_scale /*[n_f]*/, double *d_psd /*[n_rows][n_f]*/, s3_stream stream);
 
 /* Symmetric eigenproblem of the T x T Gram matrix (the step between s3_weighted_gram and the modes; the reference gets the whole
  * decomposition from flowtorch.analysis.SVD, utils.py:302-346).  The one LIBRARY call of the SVD path: rocSOLVER's dsyevd, looked up

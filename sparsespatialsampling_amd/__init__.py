@@ -20,7 +20,7 @@ if _os.environ.get("S3_KEEP_RUNTIME_PINNING") != "1":
 
 from .version import __version__
 
-__all__ = ["ReconstructionError", "reconstruct", "DMD", "__version__"]
+__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "__version__"]
 
 
 def __getattr__(name):
@@ -31,4 +31,7 @@ def __getattr__(name):
     if name == "DMD":
         from . import dmd
         return dmd.DMD
+    if name in ("welch", "SPOD"):
+        from . import spectral
+        return getattr(spectral, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

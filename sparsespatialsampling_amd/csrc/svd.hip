@@ -14,57 +14,12 @@
 // owns a 64 x 64 quarter = 4 x 4 MFMA tiles (128 accumulator VGPRs) and issues 16 MFMAs per 4 rows.  The row slices'
 // partial blocks (cut to the part that lies inside G: a T of 130 keeps 128 x 128 + 128 x 2 + 2 x 2 values per slice, not three
 // 128 x 128 blocks) are added in slice order by a second kernel (deterministic), which also mirrors the lower triangle.
-#include "common.h"
+#include "mfma_stage.h"        // tile constants, load_piece, stage_vec, the L tile and the MFMA step (shared with spectral.hip)
 
 #include <algorithm>
 #include <vector>
 
 namespace s3 {
-
-constexpr int GB = 128;            // block edge of G
-constexpr int GK = 16;             // rows of the data matrix per step
-constexpr int GLD = GB + 16;       // LDS row pitch in doubles: consecutive rows start 128 B apart modulo 256 B (no bank conflicts
-                                   // between the four 16-lane groups of a ds_read_b64)
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-// Operand staging by element type.  T = double is the matrix the interpolation kernel wrote (compute_svd); T = float is a field
-// read where it lies (the DMD of the original CFD field and of a float32 Dataloader: dmd.py) -- widened to f64 in registers,
-// BEFORE centring and weighting, so the staged value is the one the f64 staging makes of the matrix's .double() copy and the
-// two Gram matrices agree to the bit.  A 16-byte piece is PW = 2 doubles or 4 floats: 16 threads per row of a 16 x 128 panel take
-// 4 pieces at columns c0 + 32 p (double) or 2 pieces at c0 + 64 p (float), eight values per thread and panel either way.
-// VEC = elements per load instruction of a piece that lies inside the matrix: chosen per LAUNCH on the host from the alignment
-// every row start shares (stage_vec), never per lane; a piece across the matrix's edge is read element by element.
-// (T = double keeps the scalar form it always had: VEC = 1.)
-template <typename T> struct stage_traits;
-template <> struct stage_traits<double> { static constexpr int PW = 2; };
-template <> struct stage_traits<float> { static constexpr int PW = 4; };
-
-// out[j] = p[j] widened for j < avail, `fill` for the others (avail <= 0: nothing is read)
-template <typename T, int VEC, int PW>
-__device__ __forceinline__ void load_piece(const T *__restrict__ p, int avail, double fill, double (&out)[PW]) {
-    if constexpr (VEC > 1) {
-        if (avail >= PW) {
-            typedef T vec_t __attribute__((ext_vector_type(VEC)));
-#pragma unroll
-            for (int q = 0; q < PW; q += VEC) {
-                const vec_t v = *reinterpret_cast<const vec_t *>(p + q);
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) out[q + j] = (double)v[j];
-            }
-            return;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < PW; ++j) out[j] = j < avail ? (double)p[j] : fill;
-}
-
-// elements per load for float rows: every row start is (base + row * stride * 4) bytes, so the alignment all of them share is
-// the one of (base | stride * 4)
-static int stage_vec(const void *base, int64_t stride_elements) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(base) | (uintptr_t)(stride_elements * (int64_t)sizeof(float));
-    return (a & 15) == 0 ? 4 : (a & 7) == 0 ? 2 : 1;
-}
 
 template <typename T, int VEC>
 __global__ void __launch_bounds__(256)
@@ -221,22 +176,7 @@ centered_gemm_kernel(const T *__restrict__ l, int64_t m, int k, int64_t l_stride
     const int brow = threadIdx.x >> 4, c2 = (threadIdx.x & 15) * 2;
     double ra[8], rb[NJ][2];
     auto load = [&](int k0) {
-        if constexpr (sizeof(T) == 8) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int kk = k0 + lk + i;
-                ra[i] = row_ok && kk < k ? lr[kk] - mu : 0.0;      // rows / columns past the matrix contribute nothing
-            }
-        } else {                                                   // float: two 16-byte pieces of four columns, widened, then centred
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int kk = k0 + lk + 4 * h;
-                double piece[4];
-                load_piece<T, VEC, 4>(lr + kk, row_ok ? k - kk : 0, mu, piece);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) ra[4 * h + j] = piece[j] - mu;   // (mu - mu = 0 past the matrix)
-            }
-        }
+        load_l_tile<T, VEC>(lr, row_ok, k0 + lk, k, mu, ra);
         const int kb = k0 + brow;
         const double *br = b + (int64_t)(kb < k ? kb : 0) * n;
 #pragma unroll
@@ -247,8 +187,7 @@ centered_gemm_kernel(const T *__restrict__ l, int64_t m, int k, int64_t l_stride
         }
     };
     auto store = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sA[buf][lk + i][lrow] = ra[i];
+        store_l_tile(sA[buf], lk, lrow, ra);
 #pragma unroll
         for (int p = 0; p < NJ; ++p) {
             sB[buf][brow][c2 + 32 * p] = rb[p][0];
@@ -263,21 +202,7 @@ centered_gemm_kernel(const T *__restrict__ l, int64_t m, int k, int64_t l_stride
     for (int k0 = 0; k0 < k; k0 += GK) {
         const bool more = k0 + GK < k;
         if (more) load(k0 + GK);
-        const double(*pa)[GLD] = sA[buf];
-        const double(*pb)[GLD] = sB[buf];
-#pragma unroll
-        for (int k4 = 0; k4 < GK / 4; ++k4) {
-            const int kr = k4 * 4 + (lane >> 4), cl = lane & 15;
-            double a[4], bb[NJ];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = pa[kr][wi * 64 + i * 16 + cl];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) bb[j] = pb[kr][wj * (16 * NJ) + j * 16 + cl];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], bb[j], acc[i][j], 0, 0, 0);
-        }
+        mfma_step<NJ, GLD>(sA[buf], sB[buf], wi, wj, lane, acc);
         if (more) store(buf ^ 1);
         __syncthreads();
         buf ^= 1;

@@ -39,7 +39,7 @@ log = logging.getLogger(__name__)
 RANK_RANGE = 1e-4           # singular values below this fraction of the largest one are not inverted (module docstring)
 
 
-def _check_arguments(data_matrix, dt, rank, cell_area):
+def _check_arguments(data_matrix, dt, rank, cell_area, who="DMD", min_snapshots=3):
     """argument errors, raised before any device call; returns (n_cells, n_comp or None, T)"""
     if not isinstance(data_matrix, pt.Tensor):
         raise TypeError(f"data_matrix must be a torch tensor, got {type(data_matrix).__name__}")
@@ -49,8 +49,8 @@ def _check_arguments(data_matrix, dt, rank, cell_area):
     if data_matrix.dtype not in hipops.DTYPE_CODE:
         raise TypeError(f"data_matrix must be float32 or float64, got {data_matrix.dtype}")
     n_cells, t = shape[0], shape[-1]
-    if t < 3:
-        raise ValueError(f"DMD needs at least 3 snapshots, got {t}")
+    if t < min_snapshots:
+        raise ValueError(f"{who} needs at least {min_snapshots} snapshots, got {t}")
     if n_cells < 1 or (len(shape) == 3 and shape[1] < 1):
         raise ValueError(f"the data matrix has no rows: {shape}")
     if data_matrix.stride(-1) != 1:

@@ -289,6 +289,59 @@ def tall_gemm(left, b, out=None):
     return out
 
 
+def row_means(x):
+    """temporal mean of every row of a 2-D float32 / float64 device matrix, rows possibly pitched -> f64 [N] (s3_row_moments)"""
+    stride = _pitched_matrix(x, "row_means")
+    n, t = int(x.shape[0]), int(x.shape[1])
+    mean = pt.empty(n, dtype=pt.float64, device=x.device)
+    check(_lib.hip_lib().s3_row_moments(C.c_void_p(x.data_ptr()), DTYPE_CODE[x.dtype], n, t, stride, 0, _ptr(mean), C.c_void_p(0), _stream()),
+          "s3_row_moments")
+    return mean
+
+
+def _segment_arguments(x, mean, nperseg, hop, n_blk, bre, bim, who):
+    stride = _pitched_matrix(x, who)
+    n, t = int(x.shape[0]), int(x.shape[1])
+    nperseg, hop, n_blk = int(nperseg), int(hop), int(n_blk)
+    if n < 1 or nperseg < 1 or hop < 1 or n_blk < 1 or (n_blk - 1) * hop + nperseg > t:
+        raise ValueError(f"{who}: {n_blk} segments of {nperseg} samples, {hop} apart, do not fit rows of {t} samples ({n} rows)")
+    for name, b in (("bre", bre), ("bim", bim)):
+        if not (b.is_cuda and b.dtype == pt.float64 and b.dim() == 2 and b.is_contiguous() and int(b.shape[0]) == nperseg
+                and b.shape == bre.shape and int(b.shape[1]) >= 1):
+            raise TypeError(f"{who}: {name} must be a contiguous float64 device matrix [{nperseg}, n_f]")
+    if mean is not None and not (mean.is_cuda and mean.dtype == pt.float64 and mean.numel() == n):
+        raise TypeError(f"{who}: mean must be a float64 device vector [{n}]")
+    return (C.c_void_p(x.data_ptr()), DTYPE_CODE[x.dtype], n, t, stride, _ptr(mean), nperseg, hop, n_blk, _ptr(bre), _ptr(bim),
+            int(bre.shape[1]))
+
+
+def segment_dft(x, mean, nperseg, hop, n_blk, bre, bim, out=None):
+    """windowed DFT coefficients of the ``n_blk`` segments (``nperseg`` samples, ``hop`` apart) of every row of ``x`` (s3_segment_dft):
+    ``c[i, b, f] = sum_l (x[i, b hop + l] - mean[i]) (bre[l, f] + i bim[l, f])`` -> f64 [N, n_f, n_blk, 2].  ``x`` [N, T] float32 or
+    float64 on the device, rows may be pitched, read where it lies; ``mean`` f64 [N] or None; ``bre`` / ``bim`` f64 [nperseg, n_f]."""
+    args = _segment_arguments(x, mean, nperseg, hop, n_blk, bre, bim, "segment_dft")
+    shape = (args[2], args[-1], int(n_blk), 2)
+    out = pt.empty(shape, dtype=pt.float64, device=x.device) if out is None else out
+    if not (out.dtype == pt.float64 and tuple(out.shape) == shape):
+        raise TypeError(f"segment_dft: out must be float64 {shape}")
+    check(_lib.hip_lib().s3_segment_dft(*args, _ptr(out), _stream()), "s3_segment_dft")
+    return out
+
+
+def segment_psd(x, mean, nperseg, hop, n_blk, bre, bim, scale, out=None):
+    """``scale[f] * sum_b |c[i, b, f]|^2`` of the same coefficients -> f64 [N, n_f], summed in the kernel's registers (s3_segment_psd):
+    the coefficients are never written.  ``scale`` f64 device vector [n_f]."""
+    args = _segment_arguments(x, mean, nperseg, hop, n_blk, bre, bim, "segment_psd")
+    shape = (args[2], args[-1])
+    if not (scale.is_cuda and scale.dtype == pt.float64 and scale.numel() == shape[1]):
+        raise TypeError(f"segment_psd: scale must be a float64 device vector [{shape[1]}]")
+    out = pt.empty(shape, dtype=pt.float64, device=x.device) if out is None else out
+    if not (out.dtype == pt.float64 and tuple(out.shape) == shape):
+        raise TypeError(f"segment_psd: out must be float64 {shape}")
+    check(_lib.hip_lib().s3_segment_psd(*args, _ptr(scale), _ptr(out), _stream()), "s3_segment_psd")
+    return out
+
+
 # ExportData queues its device-to-host copies on a stream of their own and lets them complete behind its back (the host-logic
 # tests replace this module by CPU stand-ins that do not have the attribute: there every copy is immediate)
 ASYNC_TRANSFERS = True
