@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 12
+#define S3_ABI_VERSION 13
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -360,6 +360,44 @@ int s3_recon_error(const double *d_w /*[n,k]*/, const int32_t *d_idx /*[n,k]*/, 
                    int64_t row_len, const int32_t *d_rows /*[n] or NULL*/, const double *d_scale /*[n] or NULL*/,
                    double *d_mean /*[n_orig]*/, double *d_m2 /*[n_orig]*/, double *d_colsum /*[2][row_len]*/, void *d_scratch,
                    s3_stream stream);
+
+/* ---- spatial derivatives on a point cloud (csrc/differential.hip; no counterpart in the reference) -----------------------------
+ * Weighted least-squares gradients over the k nearest neighbours of every point of a cloud x [n][dim] (dim 2 | 3), and the
+ * quantities derived from them.  For entry j of the tables, which describes point i = d_rows[j] (d_rows NULL: i = j; launch the
+ * points in the order of s3_spatial_order), with the neighbours d_idx[j][m], m < k, none of them i itself:
+ *     dx_m = x[idx_m] - x_i,  r_m = |dx_m|,  h = max_m r_m,  dxs_m = dx_m / h,  rs_m = r_m / h
+ *     w_m  = rs_m^-power (power 0 | 1 | 2), 0 where r_m = 0 (a coincident copy says nothing about the slope)
+ *     M    = sum_m w_m dxs_m dxs_m^T = L L^T                      c[j][m][:] = w_m * M^-1 dxs_m / h
+ * A row is DEGENERATE when h = 0 or a pivot of the Cholesky factorisation (the value under its square root) is <= 2^-40 trace(M):
+ * collinear / coplanar neighbours.  Its coefficients are all zero and d_flag[j] = 1 (0 otherwise); *h_n_degenerate counts them.
+ * s3_grad_coeff returns when the tables are complete.
+ *
+ * s3_grad_apply, one launch per snapshot batch: d_field rows [n_comp][row_len] f32 or f64 (dtype: S3_DTYPE_*) with pitch in_stride
+ * ELEMENTS (0 = n_comp * row_len), read where they lie; row r of the field belongs to point r.  With
+ *     G[a][b][t] = sum_{m<k} c[j][m][b] * (f[idx_m][a][t] - f[i][a][t])      f64 fma chain over m = 0..k-1 from 0; the difference is
+ *                                                                           formed in f64 first: a constant field gives exact zeros
+ * row i = d_rows[j] of d_out (f64, pitch out_stride elements, 0 = n_out * row_len) receives [n_out][row_len]:
+ *     S3_GRAD_GRADIENT             G, ordered [comp][axis][t]                          n_out = n_comp * dim
+ *     S3_GRAD_MAGNITUDE            sqrt(sum_b G[a][b]^2) per component a               n_out = n_comp
+ *     S3_GRAD_DIVERGENCE           sum_a G[a][a]                                       n_out = 1        (these four: n_comp == dim)
+ *     S3_GRAD_VORTICITY            G[1][0] - G[0][1] in 2-D; (G[2][1] - G[1][2], G[0][2] - G[2][0], G[1][0] - G[0][1]) in 3-D
+ *     S3_GRAD_VORTICITY_MAGNITUDE  Euclidean norm of the vorticity                     n_out = 1
+ *     S3_GRAD_Q                    -1/2 sum_ab G[a][b] G[b][a]                         n_out = 1
+ * n_comp is 1, 2 or 3 per launch; a wider field goes in groups of components (offset d_field and d_out, keep the pitches).  The
+ * gradient entries stay in registers: only the requested quantity is written.  d_idx holds rows of the field (< n, not checked on
+ * the device).  No floating-point atomics: the same inputs give the same bits on every run, whatever row_len and n_comp. */
+#define S3_GRAD_GRADIENT 0
+#define S3_GRAD_MAGNITUDE 1
+#define S3_GRAD_DIVERGENCE 2
+#define S3_GRAD_VORTICITY 3
+#define S3_GRAD_VORTICITY_MAGNITUDE 4
+#define S3_GRAD_Q 5
+int s3_grad_coeff(const double *d_pts /*[n,dim]*/, int64_t n, int dim, const int32_t *d_idx /*[n,k]*/, int k, int power,
+                  const int32_t *d_rows /*[n] or NULL*/, double *d_coef /*[n,k,dim]*/, uint8_t *d_flag /*[n]*/,
+                  int64_t *h_n_degenerate, s3_stream stream);
+int s3_grad_apply(const double *d_coef /*[n,k,dim]*/, const int32_t *d_idx /*[n,k]*/, int64_t n, int k, int dim, const void *d_field,
+                  int dtype, int n_comp, int64_t row_len, int64_t in_stride, const int32_t *d_rows /*[n] or NULL*/, int mode,
+                  double *d_out, int64_t out_stride, s3_stream stream);
 
 /* ---- yardsticks of the measurement (bench.py's roofline line; no counterpart in the reference, not on any product path) ----
  * s3_yard_stream      a hand-written streaming kernel over d_src: every lane reads `reads` 16-byte vectors (coalesced) and

@@ -20,7 +20,7 @@ if _os.environ.get("S3_KEEP_RUNTIME_PINNING") != "1":
 
 from .version import __version__
 
-__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "__version__"]
+__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "__version__"]
 
 
 def __getattr__(name):
@@ -34,4 +34,7 @@ def __getattr__(name):
     if name in ("welch", "SPOD"):
         from . import spectral
         return getattr(spectral, name)
+    if name == "Gradient":
+        from . import differential
+        return differential.Gradient
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -239,6 +239,83 @@ def recon_error(w, idx, grid, orig, rows=None, scale=None, mean=None, m2=None):
     return mean, m2, colsum
 
 
+GRAD_MODES = {"gradient": 0, "magnitude": 1, "divergence": 2, "vorticity": 3, "vorticity_magnitude": 4, "q": 5}    # S3_GRAD_* (s3hip.h)
+GRAD_MAX_K = 63             # S3_MAX_K - 1: the search behind a stencil asks for one neighbour more, the point itself
+
+
+def grad_n_out(mode, dim, n_comp):
+    """values per point and snapshot of ``grad_apply``'s modes"""
+    return {"gradient": n_comp * dim, "magnitude": n_comp, "vorticity": 1 if dim == 2 else 3}.get(mode, 1)
+
+
+def grad_coeff(points, idx, power=2, rows=None):
+    """least-squares gradient coefficients of a cloud (s3_grad_coeff).  ``points`` f64 [n, 2 | 3] and ``idx`` int32 [n, k] on the
+    device; entry j of ``idx`` holds the neighbours of point ``rows[j]`` (``rows`` int32 [n] or None: point j), the point itself
+    not among them.  -> ``(coef f64 [n, k, dim], flag uint8 [n], n_degenerate)`` in the order of ``idx``: a degenerate row
+    (collinear / coplanar / coincident neighbours) has zero coefficients and flag 1."""
+    if not (points.is_cuda and points.dtype == pt.float64 and points.dim() == 2 and int(points.shape[1]) in (2, 3)):
+        raise TypeError("grad_coeff: points must be a float64 device tensor [n, 2 | 3]")
+    n, dim = int(points.shape[0]), int(points.shape[1])
+    if not (idx.is_cuda and idx.dtype == pt.int32 and idx.dim() == 2 and int(idx.shape[0]) == n):
+        raise TypeError(f"grad_coeff: idx must be an int32 device tensor [{n}, k]")
+    if rows is not None and not (rows.is_cuda and rows.dtype == pt.int32 and rows.numel() == n):
+        raise TypeError(f"grad_coeff: rows must be an int32 device tensor [{n}]")
+    k = int(idx.shape[1])
+    coef = pt.empty((n, k, dim), dtype=pt.float64, device=points.device)
+    flag = pt.empty(n, dtype=pt.uint8, device=points.device)
+    n_deg = C.c_int64(0)
+    check(_lib.hip_lib().s3_grad_coeff(_ptr(points), n, dim, _ptr(idx), k, int(power), _ptr(rows), _ptr(coef), _ptr(flag),
+                                       C.byref(n_deg), _stream()), "s3_grad_coeff")
+    return coef, flag, n_deg.value
+
+
+def grad_apply(coef, idx, field, mode, rows=None, out=None):
+    """the fused gradient launch (s3_grad_apply): ``mode`` is a key of ``GRAD_MODES``.  ``coef`` f64 [n, k, dim] / ``idx`` int32
+    [n, k] as ``grad_coeff`` made them (entry j: point ``rows[j]``), ``field`` float32 / float64 on the device: [n] (one snapshot),
+    [n, T] (rows may be pitched: read where they lie) or [n, n_comp, T] contiguous.  -> f64 [n, n_out, T] (``grad_n_out``;
+    "gradient" is ordered [comp][axis]), written into ``out`` when given.  The kernel takes up to three components per launch:
+    a wider field goes in groups, for "gradient" and "magnitude" only."""
+    if mode not in GRAD_MODES:
+        raise ValueError(f"grad_apply: unknown mode {mode!r}, expected one of {sorted(GRAD_MODES)}")
+    if not (coef.is_cuda and coef.dtype == pt.float64 and coef.dim() == 3 and idx.is_cuda and idx.dtype == pt.int32
+            and tuple(idx.shape) == tuple(coef.shape[:2])):
+        raise TypeError("grad_apply: coef must be float64 [n, k, dim], idx int32 [n, k], both on the device")
+    n, k, dim = (int(v) for v in coef.shape)
+    if not (isinstance(field, pt.Tensor) and field.is_cuda and field.dtype in DTYPE_CODE and 1 <= field.dim() <= 3):
+        raise TypeError("grad_apply: float32 / float64 device field [n], [n, T] or [n, n_comp, T] required")
+    if int(field.shape[0]) != n:
+        raise ValueError(f"grad_apply: the field has {int(field.shape[0])} rows, the stencils {n}")
+    if field.dim() == 3:
+        n_comp, t = int(field.shape[1]), int(field.shape[2])
+        if not field.is_contiguous():
+            raise TypeError("grad_apply: a field [n, n_comp, T] must be contiguous")
+        in_stride = n_comp * t
+    else:
+        n_comp = 1
+        t, in_stride = _pitched_rows(field, "grad_apply(field)")
+    if t < 1 or n_comp < 1:
+        raise ValueError(f"grad_apply: empty field {tuple(field.shape)}")
+    vector_mode = mode not in ("gradient", "magnitude")
+    if vector_mode and n_comp != dim:
+        raise ValueError(f"grad_apply: {mode} needs a vector field [n, {dim}, T], got {tuple(field.shape)}")
+    if rows is not None and not (rows.is_cuda and rows.dtype == pt.int32 and rows.numel() == n):
+        raise TypeError(f"grad_apply: rows must be an int32 device tensor [{n}]")
+    n_out = grad_n_out(mode, dim, n_comp)
+    if out is None:
+        out = pt.empty((n, n_out, t), dtype=pt.float64, device=field.device)
+    elif not (isinstance(out, pt.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == pt.float64
+              and out.numel() == n * n_out * t and out.device == field.device):
+        raise TypeError(f"grad_apply: out must be a contiguous float64 device tensor of {n} x {n_out} x {t} values")
+    lib, item = _lib.hip_lib(), field.element_size()
+    per_comp = dim if mode == "gradient" else 1
+    for c0 in range(0, n_comp, 3) if n_comp > 3 else (0,):
+        group = min(3, n_comp - c0)
+        check(lib.s3_grad_apply(_ptr(coef), _ptr(idx), n, k, dim, C.c_void_p(field.data_ptr() + c0 * t * item), DTYPE_CODE[field.dtype],
+                                group, t, in_stride, _ptr(rows), GRAD_MODES[mode], C.c_void_p(out.data_ptr() + c0 * per_comp * t * 8),
+                                n_out * t, _stream()), "s3_grad_apply")
+    return out
+
+
 def _pitched_matrix(t, who):
     """row pitch in elements of a 2-D f32 / f64 device matrix with unit inner stride, read where it lies"""
     if not (t.is_cuda and t.dtype in DTYPE_CODE and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
