@@ -16,17 +16,15 @@
 // gathered from the field itself (the neighbours of consecutive points of the Hilbert launch order overlap: L2 / Infinity Cache),
 // n_out * T f64 values are written.  The n_comp x dim gradient entries never leave the registers.
 //
-// Work split (the one of recon_kernel, csrc/recon.hip, without its reductions): a workgroup (256 threads) owns GRAD_BLOCK
-// consecutive points of the launch order.  Its threads form 256/LP point slots of LP lanes (LP = 4..64, the power of two that
-// covers a row's VEC-wide pieces); lane l of a slot owns the columns [(chunk*LP + l)*VEC, +VEC) of EVERY component.  The block is
-// walked in stages of stage_pts points (64 unless LDS is short: grad_lds): the coefficients / ids of a stage go through LDS between
-// one pair of barriers, then the slots sweep the stage without a barrier.  Rows longer than LP*VEC columns are swept in chunks
-// (chunk loop outside: the block's tables are staged once per chunk).
+// Work split: the point slots of csrc/point_slots.h, as in recon_kernel (csrc/recon.hip) without its reductions.  A workgroup owns
+// GRAD_BLOCK consecutive points of the launch order; lane l of a slot owns the columns [(chunk*LP + l)*VEC, +VEC) of EVERY component;
+// the staged tables are the coefficients and ids.
 //
 // Order of every floating-point sum: an f64 fma chain over the neighbours m = 0..k-1 per (component, axis, column), independent
 // of row_len, VEC, LP and n_comp; the derived quantities are formed from the finished chains in a fixed order.  No atomics on
 // floating-point values: the same inputs give the same bits on every run.
-#include "common.h"
+#include "point_slots.h"
+#include "typed_rows.h"
 
 #include <cmath>
 
@@ -34,10 +32,9 @@ namespace s3 {
 
 namespace {
 
-constexpr int GRAD_THREADS = 256;
+constexpr int GRAD_THREADS = POINT_THREADS;
 constexpr int GRAD_BLOCK = 256;         // points per workgroup
 constexpr int GRAD_FLIGHT = 4;          // neighbour rows (all components) a lane has in flight before the first fma
-constexpr size_t GRAD_LDS_MAX = 48 * 1024;
 
 // ---- coefficients ---------------------------------------------------------------------------------------------------------
 template <int DIM>
@@ -149,23 +146,6 @@ grad_coeff_kernel(const double *__restrict__ pts, int64_t n, const int32_t *__re
 }
 
 // ---- apply ----------------------------------------------------------------------------------------------------------------
-template <typename T, int VEC>
-struct GVec;
-template <> struct GVec<float, 4> { using type = float4; };
-template <> struct GVec<float, 1> { using type = float; };
-template <> struct GVec<double, 2> { using type = double2; };
-template <> struct GVec<double, 1> { using type = double; };
-
-template <typename T, int VEC>
-__device__ __forceinline__ typename GVec<T, VEC>::type gload(const T *__restrict__ p) {
-    return *reinterpret_cast<const typename GVec<T, VEC>::type *>(p);
-}
-
-template <typename T, int VEC>
-__device__ __forceinline__ double gelem(const typename GVec<T, VEC>::type &raw, int i) {
-    return (double)reinterpret_cast<const T *>(&raw)[i];
-}
-
 __host__ __device__ constexpr int grad_n_out(int mode, int dim, int n_comp) {
     return mode == S3_GRAD_GRADIENT ? n_comp * dim : mode == S3_GRAD_MAGNITUDE ? n_comp : mode == S3_GRAD_VORTICITY ? (dim == 2 ? 1 : 3) : 1;
 }
@@ -221,17 +201,14 @@ __global__ void __launch_bounds__(GRAD_THREADS)
 grad_apply_kernel(const double *__restrict__ coef, const int32_t *__restrict__ idx, int64_t n, int k, const T *__restrict__ field,
                   int64_t row_len, int64_t in_stride, const int32_t *__restrict__ rows, double *__restrict__ out, int64_t out_stride,
                   int lp, int stage_pts, int n_chunks, int64_t n_blocks, int64_t blocks_per_xcd) {
-    using V = typename GVec<T, VEC>::type;
+    using V = typename RowVec<T, VEC>::type;
     constexpr int NOUT = grad_n_out(MODE, DIM, NCOMP);
     extern __shared__ double lds[];
     double *s_c = lds;                                                                    // [stage_pts * k * DIM]
     int32_t *s_i = reinterpret_cast<int32_t *>(s_c + (size_t)stage_pts * k * DIM);        // [stage_pts * k]
     const int pg = GRAD_THREADS / lp;                                           // point slots = points per pass (divides stage_pts)
 
-    // consecutive blocks of the spatial order gather the same field rows: workgroups that share blockIdx % 8 share an XCD's L2,
-    // so each of them walks one contiguous eighth of the blocks (speed only)
-    const int64_t b = blockIdx.x;
-    const int64_t blk = (b & 7) * blocks_per_xcd + (b >> 3);
+    const int64_t blk = xcd_block(blockIdx.x, blocks_per_xcd);
     if (blk >= n_blocks) return;
     const int64_t p0 = blk * GRAD_BLOCK;
     const int n_p = (int)min((int64_t)GRAD_BLOCK, n - p0);
@@ -260,9 +237,9 @@ grad_apply_kernel(const double *__restrict__ coef, const int32_t *__restrict__ i
                 double fc[NCOMP][VEC], acc[NCOMP][DIM][VEC];
 #pragma unroll
                 for (int c = 0; c < NCOMP; ++c) {
-                    const V raw = gload<T, VEC>(col + orow * in_stride + c * row_len);
+                    const V raw = row_load<T, VEC>(col + orow * in_stride + c * row_len);
 #pragma unroll
-                    for (int i = 0; i < VEC; ++i) fc[c][i] = gelem<T, VEC>(raw, i);
+                    for (int i = 0; i < VEC; ++i) fc[c][i] = row_elem<T, VEC>(raw, i);
 #pragma unroll
                     for (int a = 0; a < DIM; ++a)
 #pragma unroll
@@ -275,7 +252,7 @@ grad_apply_kernel(const double *__restrict__ coef, const int32_t *__restrict__ i
                     for (int u = 0; u < GRAD_FLIGHT; ++u) {
                         const T *row = col + (int64_t)ip[m + u] * in_stride;
 #pragma unroll
-                        for (int c = 0; c < NCOMP; ++c) raw[u][c] = gload<T, VEC>(row + c * row_len);
+                        for (int c = 0; c < NCOMP; ++c) raw[u][c] = row_load<T, VEC>(row + c * row_len);
                     }
 #pragma unroll
                     for (int u = 0; u < GRAD_FLIGHT; ++u) {
@@ -286,7 +263,7 @@ grad_apply_kernel(const double *__restrict__ coef, const int32_t *__restrict__ i
                         for (int c = 0; c < NCOMP; ++c)
 #pragma unroll
                             for (int i = 0; i < VEC; ++i) {
-                                const double d = gelem<T, VEC>(raw[u][c], i) - fc[c][i];
+                                const double d = row_elem<T, VEC>(raw[u][c], i) - fc[c][i];
 #pragma unroll
                                 for (int a = 0; a < DIM; ++a) acc[c][a][i] = fma(cu[a], d, acc[c][a][i]);
                             }
@@ -296,7 +273,7 @@ grad_apply_kernel(const double *__restrict__ coef, const int32_t *__restrict__ i
                     V raw[NCOMP];
                     const T *row = col + (int64_t)ip[m] * in_stride;
 #pragma unroll
-                    for (int c = 0; c < NCOMP; ++c) raw[c] = gload<T, VEC>(row + c * row_len);
+                    for (int c = 0; c < NCOMP; ++c) raw[c] = row_load<T, VEC>(row + c * row_len);
                     double cu[DIM];
 #pragma unroll
                     for (int a = 0; a < DIM; ++a) cu[a] = cp[m * DIM + a];
@@ -304,7 +281,7 @@ grad_apply_kernel(const double *__restrict__ coef, const int32_t *__restrict__ i
                     for (int c = 0; c < NCOMP; ++c)
 #pragma unroll
                         for (int i = 0; i < VEC; ++i) {
-                            const double d = gelem<T, VEC>(raw[c], i) - fc[c][i];
+                            const double d = row_elem<T, VEC>(raw[c], i) - fc[c][i];
 #pragma unroll
                             for (int a = 0; a < DIM; ++a) acc[c][a][i] = fma(cu[a], d, acc[c][a][i]);
                         }
@@ -327,16 +304,6 @@ grad_apply_kernel(const double *__restrict__ coef, const int32_t *__restrict__ i
     }
 }
 
-// LDS of a launch with `lanes` lanes per point slot: the coefficients / ids of one stage of points -- up to 64 points (46.6 KB at
-// k = 26 in 3-D), halved while that exceeds GRAD_LDS_MAX, never fewer than one pass of the slots (256 / lanes points)
-struct GradLds { int stage_pts; size_t bytes; };
-GradLds grad_lds(int lanes, int k, int dim) {
-    const size_t per_point = (size_t)k * (sizeof(double) * dim + sizeof(int32_t));
-    int stage_pts = 64;
-    while (stage_pts > GRAD_THREADS / lanes && stage_pts * per_point > GRAD_LDS_MAX) stage_pts /= 2;
-    return GradLds{stage_pts, stage_pts * per_point};
-}
-
 struct GradArgs {
     const double *coef;
     const int32_t *idx;
@@ -352,23 +319,16 @@ struct GradArgs {
 
 template <typename T, int VEC, int DIM, int NCOMP, int MODE>
 int launch_grad(const GradArgs &g) {
-    const int64_t pieces = g.row_len / VEC;
-    int lp = 4;                                             // at least 4 lanes per point: at most 64 points' tables in LDS
-    while (lp < 64 && lp < pieces) lp *= 2;
-    GradLds shape = grad_lds(lp, g.k, DIM);
-    while (lp < 64 && shape.bytes > GRAD_LDS_MAX) {         // (short rows with many neighbours: fewer, wider slots)
-        lp *= 2;
-        shape = grad_lds(lp, g.k, DIM);
-    }
-    const int64_t n_chunks = (pieces + lp - 1) / lp;
-    S3_REQUIRE(n_chunks < ((int64_t)1 << 20), "s3_grad_apply: row_len %lld too long", (long long)g.row_len);
-    S3_REQUIRE(shape.bytes <= GRAD_LDS_MAX, "s3_grad_apply: %zu bytes of LDS needed", shape.bytes);
+    // LDS (slot_shape, csrc/point_slots.h): per point of a stage its coefficients and ids (64 points: 46.6 KB at k = 26 in 3-D)
+    SlotShape shape;
+    if (const int rc = slot_shape("s3_grad_apply", g.row_len, g.row_len / VEC, (size_t)g.k * (sizeof(double) * DIM + sizeof(int32_t)), 0, 0, shape))
+        return rc;
     const int64_t n_blocks = (g.n + GRAD_BLOCK - 1) / GRAD_BLOCK;
-    const int64_t blocks_per_xcd = (n_blocks + 7) / 8;
-    S3_REQUIRE(blocks_per_xcd * 8 < ((int64_t)1 << 31), "s3_grad_apply: too many points");
-    grad_apply_kernel<T, VEC, DIM, NCOMP, MODE><<<(unsigned)(blocks_per_xcd * 8), GRAD_THREADS, shape.bytes, g.st>>>(
-        g.coef, g.idx, g.n, g.k, static_cast<const T *>(g.field), g.row_len, g.in_stride, g.rows, g.out, g.out_stride, lp,
-        shape.stage_pts, (int)n_chunks, n_blocks, blocks_per_xcd);
+    const XcdGrid xcd = xcd_grid(n_blocks);
+    S3_REQUIRE(xcd.fits(), "s3_grad_apply: too many points");
+    grad_apply_kernel<T, VEC, DIM, NCOMP, MODE><<<(unsigned)xcd.grid, GRAD_THREADS, shape.lds_bytes, g.st>>>(
+        g.coef, g.idx, g.n, g.k, static_cast<const T *>(g.field), g.row_len, g.in_stride, g.rows, g.out, g.out_stride, shape.lanes,
+        shape.stage_pts, (int)shape.n_chunks, n_blocks, xcd.per_xcd);
     S3_LAUNCH_CHECK();
     return S3_OK;
 }
@@ -390,11 +350,6 @@ int grad_by_mode(const GradArgs &g, int n_comp, int mode) {
     case S3_GRAD_VORTICITY_MAGNITUDE: return launch_grad<T, VEC, DIM, DIM, S3_GRAD_VORTICITY_MAGNITUDE>(g);
     default: return launch_grad<T, VEC, DIM, DIM, S3_GRAD_Q>(g);
     }
-}
-
-template <typename T, int VEC>
-int grad_by_dim(const GradArgs &g, int dim, int n_comp, int mode) {
-    return dim == 2 ? grad_by_mode<T, VEC, 2>(g, n_comp, mode) : grad_by_mode<T, VEC, 3>(g, n_comp, mode);
 }
 
 }  // namespace
@@ -449,14 +404,12 @@ int s3_grad_apply(const double *d_coef, const int32_t *d_idx, int64_t n, int k, 
     if (n == 0) return S3_OK;
     S3_REQUIRE(d_coef && d_idx && d_field && d_out, "s3_grad_apply: null array");
     const GradArgs g{d_coef, d_idx, n, k, d_field, row_len, in_stride, d_rows, d_out, out_stride, as_stream(stream)};
-    const uintptr_t a_field = reinterpret_cast<uintptr_t>(d_field);
     // the width of a lane's piece: every component row of every field row must start on a 16-byte boundary
-    if (dtype == S3_DTYPE_F32) {
-        if (row_len % 4 == 0 && in_stride % 4 == 0 && a_field % 16 == 0) return grad_by_dim<float, 4>(g, dim, n_comp, mode);
-        return grad_by_dim<float, 1>(g, dim, n_comp, mode);
-    }
-    if (row_len % 2 == 0 && in_stride % 2 == 0 && a_field % 16 == 0) return grad_by_dim<double, 2>(g, dim, n_comp, mode);
-    return grad_by_dim<double, 1>(g, dim, n_comp, mode);
+    return dispatch_rows<WidestRowWidth>(dtype, row_width<WidestRowWidth>(dtype, d_field, row_len, in_stride), [&](auto row) {
+        using T = typename decltype(row)::type;
+        constexpr int VEC = decltype(row)::vec;
+        return dim == 2 ? grad_by_mode<T, VEC, 2>(g, n_comp, mode) : grad_by_mode<T, VEC, 3>(g, n_comp, mode);
+    });
 }
 
 }  // extern "C"

@@ -13,43 +13,16 @@
 // product and then sums; the difference is <= k ulp, the contract is 1e-5 relative).  No MFMA: this is a gather +
 // weighted reduce with ~0.5 flop per byte.
 //
-// Workgroup -> tile mapping is XCD-aware: workgroups that share `blockIdx % 8` run on the same XCD (MI355X deals
-// workgroups round-robin over its 8 XCDs), so XCD x sweeps the x-th contiguous eighth of the tiles and spatially
-// adjacent cells (which share neighbours) hit the same 4 MiB L2.
-#include "common.h"
+// Workgroup -> tile mapping is XCD-aware (xcd_block, csrc/point_slots.h): XCD x sweeps the x-th contiguous eighth of the
+// tiles and spatially adjacent cells (which share neighbours) hit the same 4 MiB L2.
+#include "point_slots.h"
+#include "typed_rows.h"
+
+#include <type_traits>
 
 namespace s3 {
 
 constexpr int INTERP_BLOCK = 256;
-
-template <typename T, int VEC>
-struct VecT;
-template <> struct VecT<float, 4> { using type = float4; };
-template <> struct VecT<float, 2> { using type = float2; };
-template <> struct VecT<float, 1> { using type = float; };
-template <> struct VecT<double, 2> { using type = double2; };
-template <> struct VecT<double, 1> { using type = double; };
-
-template <typename T, int VEC>
-__device__ __forceinline__ void load_vec(const T *__restrict__ p, double (&v)[VEC]) {
-    using V = typename VecT<T, VEC>::type;
-    V raw = *reinterpret_cast<const V *>(p);
-    const T *e = reinterpret_cast<const T *>(&raw);
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) v[i] = (double)e[i];
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_vec(double *__restrict__ p, const double (&a)[VEC]) {
-    if constexpr (VEC == 4) {
-        *reinterpret_cast<double2 *>(p) = make_double2(a[0], a[1]);
-        *reinterpret_cast<double2 *>(p + 2) = make_double2(a[2], a[3]);
-    } else if constexpr (VEC == 2) {
-        *reinterpret_cast<double2 *>(p) = make_double2(a[0], a[1]);
-    } else {
-        p[0] = a[0];
-    }
-}
 
 template <typename T, int VEC>
 __global__ void __launch_bounds__(INTERP_BLOCK)
@@ -60,9 +33,7 @@ interp_kernel(const double *__restrict__ w, const int32_t *__restrict__ idx, int
     double *s_w = lds;                                                  // [tc*k]
     int32_t *s_idx = reinterpret_cast<int32_t *>(lds + (size_t)tc * k); // [tc*k]
 
-    // XCD-aware tile assignment (speed only)
-    const int64_t b = blockIdx.x;
-    const int64_t tile = (b & 7) * tiles_per_xcd + (b >> 3);
+    const int64_t tile = xcd_block(blockIdx.x, tiles_per_xcd);
     if (tile >= n_tiles) return;
     const int64_t c0 = tile * tc;
     const int n_c = (int)min((int64_t)tc, nc - c0);
@@ -91,7 +62,7 @@ interp_kernel(const double *__restrict__ w, const int32_t *__restrict__ idx, int
         for (; m + 8 <= k; m += 8) {
             double v[8][VEC];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) load_vec<T, VEC>(col + (int64_t)ip[m + u] * row_len, v[u]);
+            for (int u = 0; u < 8; ++u) row_load_wide<T, VEC>(col + (int64_t)ip[m + u] * row_len, v[u]);
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const double wu = wp[m + u];
@@ -102,10 +73,10 @@ interp_kernel(const double *__restrict__ w, const int32_t *__restrict__ idx, int
         for (; m + 4 <= k; m += 4) {
             double v0[VEC], v1[VEC], v2[VEC], v3[VEC];
             const int64_t r0 = ip[m], r1 = ip[m + 1], r2 = ip[m + 2], r3 = ip[m + 3];
-            load_vec<T, VEC>(col + r0 * row_len, v0);
-            load_vec<T, VEC>(col + r1 * row_len, v1);
-            load_vec<T, VEC>(col + r2 * row_len, v2);
-            load_vec<T, VEC>(col + r3 * row_len, v3);
+            row_load_wide<T, VEC>(col + r0 * row_len, v0);
+            row_load_wide<T, VEC>(col + r1 * row_len, v1);
+            row_load_wide<T, VEC>(col + r2 * row_len, v2);
+            row_load_wide<T, VEC>(col + r3 * row_len, v3);
             const double w0 = wp[m], w1 = wp[m + 1], w2 = wp[m + 2], w3 = wp[m + 3];
 #pragma unroll
             for (int i = 0; i < VEC; ++i) {
@@ -117,12 +88,12 @@ interp_kernel(const double *__restrict__ w, const int32_t *__restrict__ idx, int
         }
         for (; m < k; ++m) {
             double v0[VEC];
-            load_vec<T, VEC>(col + (int64_t)ip[m] * row_len, v0);
+            row_load_wide<T, VEC>(col + (int64_t)ip[m] * row_len, v0);
             const double w0 = wp[m];
 #pragma unroll
             for (int i = 0; i < VEC; ++i) acc[i] = fma(w0, v0[i], acc[i]);
         }
-        store_vec<VEC>(out + (c0 + cl) * row_len + (int64_t)lv * VEC, acc);
+        row_store<VEC>(out + (c0 + cl) * row_len + (int64_t)lv * VEC, acc);
     }
 }
 
@@ -292,13 +263,12 @@ static int launch_interp(const double *w, const int32_t *idx, int64_t nc, int k,
     if (tc < 1) tc = 1;
     if (tc > nc) tc = nc;
     const int64_t n_tiles = (nc + tc - 1) / tc;
-    const int64_t tiles_per_xcd = (n_tiles + 7) / 8;
-    const int64_t grid = tiles_per_xcd * 8;
-    S3_REQUIRE(grid < ((int64_t)1 << 31), "s3_interp: too many tiles (%lld)", (long long)grid);
+    const XcdGrid xcd = xcd_grid(n_tiles);
+    S3_REQUIRE(xcd.fits(), "s3_interp: too many tiles (%lld)", (long long)xcd.grid);
     S3_REQUIRE(tc * lv_count < ((int64_t)1 << 31), "s3_interp: row_len %lld too long", (long long)row_len);
     size_t lds = (size_t)tc * k * (sizeof(double) + sizeof(int32_t));
-    interp_kernel<T, VEC><<<(unsigned)grid, INTERP_BLOCK, lds, st>>>(w, idx, nc, k, static_cast<const T *>(data),
-                                                                    row_len, out, (int)tc, n_tiles, tiles_per_xcd);
+    interp_kernel<T, VEC><<<(unsigned)xcd.grid, INTERP_BLOCK, lds, st>>>(w, idx, nc, k, static_cast<const T *>(data),
+                                                                        row_len, out, (int)tc, n_tiles, xcd.per_xcd);
     S3_LAUNCH_CHECK();
     return S3_OK;
 }
@@ -319,17 +289,11 @@ int s3_interp(const double *d_w, const int32_t *d_idx, int64_t nc, int k, const 
     S3_REQUIRE(d_w && d_idx && d_data && d_out, "s3_interp: null array");
     S3_REQUIRE(n_src < ((int64_t)1 << 31), "s3_interp: n_src must fit int32");
     hipStream_t st = as_stream(stream);
-    const uintptr_t a_in = reinterpret_cast<uintptr_t>(d_data), a_out = reinterpret_cast<uintptr_t>(d_out);
-    if (dtype == S3_DTYPE_F32) {
-        if (row_len % 4 == 0 && a_in % 16 == 0 && a_out % 16 == 0)
-            return launch_interp<float, 4>(d_w, d_idx, nc, k, d_data, row_len, d_out, st);
-        if (row_len % 2 == 0 && a_in % 8 == 0 && a_out % 16 == 0)
-            return launch_interp<float, 2>(d_w, d_idx, nc, k, d_data, row_len, d_out, st);
-        return launch_interp<float, 1>(d_w, d_idx, nc, k, d_data, row_len, d_out, st);
-    }
-    if (row_len % 2 == 0 && a_in % 16 == 0 && a_out % 16 == 0)
-        return launch_interp<double, 2>(d_w, d_idx, nc, k, d_data, row_len, d_out, st);
-    return launch_interp<double, 1>(d_w, d_idx, nc, k, d_data, row_len, d_out, st);
+    // (the output is stored 16 bytes at a time whatever the width of the loads)
+    const int width = reinterpret_cast<uintptr_t>(d_out) % 16 == 0 ? row_width<EveryRowWidth>(dtype, d_data, row_len) : 1;
+    return dispatch_rows<EveryRowWidth>(dtype, width, [&](auto row) {
+        return launch_interp<typename decltype(row)::type, decltype(row)::vec>(d_w, d_idx, nc, k, d_data, row_len, d_out, st);
+    });
 }
 
 int s3_snapshot_major_rows_as(const double *d_in, int64_t nc, int n_comp, int64_t n_snapshots, const int32_t *d_rows,
@@ -404,24 +368,19 @@ int s3_cell_major(const void *d_in, int in_dtype, int64_t n_snapshots, int64_t n
     S3_REQUIRE(gx < ((int64_t)1 << 31) && gy <= 65535, "s3_cell_major: shape too large for one launch");
     const dim3 grid((unsigned)gx, (unsigned)gy);
     hipStream_t st = as_stream(stream);
-#define S3_CELL_MAJOR(IN, OUT, TW)                                                                                            \
-    cell_major_kernel<IN, OUT, TW><<<grid, 256, 0, st>>>(static_cast<const IN *>(d_in), n_rows, n_snapshots,                   \
-                                                         static_cast<Word<OUT>::type *>(d_out), out_stride, t0)
-#define S3_CELL_MAJOR_TW(IN, OUT)                                                                                             \
-    do {                                                                                                                      \
-        if (tw == 4) S3_CELL_MAJOR(IN, OUT, 4);                                                                               \
-        else if (tw == 16) S3_CELL_MAJOR(IN, OUT, 16);                                                                        \
-        else S3_CELL_MAJOR(IN, OUT, 32);                                                                                      \
-    } while (0)
-    if (in_dtype == S3_DTYPE_F32) {
-        if (out_dtype == S3_DTYPE_F32) S3_CELL_MAJOR_TW(float, float);
-        else S3_CELL_MAJOR_TW(float, double);
-    } else {
-        if (out_dtype == S3_DTYPE_F32) S3_CELL_MAJOR_TW(double, float);
-        else S3_CELL_MAJOR_TW(double, double);
-    }
-#undef S3_CELL_MAJOR_TW
-#undef S3_CELL_MAJOR
+    dispatch_rows<ScalarRows>(in_dtype, 1, [&](auto in) {
+        dispatch_rows<ScalarRows>(out_dtype, 1, [&](auto o) {
+            using IN = typename decltype(in)::type;
+            using OUT = typename decltype(o)::type;
+            auto launch = [&](auto tile) {
+                cell_major_kernel<IN, OUT, decltype(tile)::value><<<grid, 256, 0, st>>>(static_cast<const IN *>(d_in), n_rows, n_snapshots,
+                                                                                       static_cast<typename Word<OUT>::type *>(d_out), out_stride, t0);
+            };
+            if (tw == 4) launch(std::integral_constant<int, 4>{});
+            else if (tw == 16) launch(std::integral_constant<int, 16>{});
+            else launch(std::integral_constant<int, 32>{});
+        });
+    });
     S3_LAUNCH_CHECK();
     return S3_OK;
 }

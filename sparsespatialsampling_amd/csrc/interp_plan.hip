@@ -23,6 +23,7 @@
 // workload), which moves the kernel from the Infinity-Cache gather bound towards the HBM bound.
 #include "common.h"
 #include "plan_build.h"
+#include "point_slots.h"
 
 #include <algorithm>
 #include <exception>
@@ -197,7 +198,7 @@ interp_planned_short_kernel(const int32_t *__restrict__ perm, const int32_t *__r
     int32_t *s_cell = reinterpret_cast<int32_t *>(s_loc + (size_t)k * TC);       // [TC] output rows of the tile's cells
 
     const int64_t b = blockIdx.x;
-    const int64_t tile = (b & 7) * tiles_per_xcd + (b >> 3);     // XCD-aware (speed only)
+    const int64_t tile = xcd_block(b, tiles_per_xcd);            // XCD-aware (speed only)
     if (tile >= n_tiles) return;
     const int c_begin = tile_cell_begin[tile], n_c = tile_cell_begin[tile + 1] - c_begin;
     const int r_begin = tile_row_begin[tile], n_r = tile_row_begin[tile + 1] - r_begin;
@@ -268,7 +269,7 @@ interp_planned_short_reg_kernel(const int32_t *__restrict__ perm, const int32_t 
     V *s_data = reinterpret_cast<V *>(lds_raw);                  // [n_r][vc]
 
     const int64_t b = blockIdx.x;
-    const int64_t tile = (b & 7) * tiles_per_xcd + (b >> 3);
+    const int64_t tile = xcd_block(b, tiles_per_xcd);
     if (tile >= n_tiles) return;
     const int c_begin = tile_cell_begin[tile], n_c = tile_cell_begin[tile + 1] - c_begin;
     const int r_begin = tile_row_begin[tile], n_r = tile_row_begin[tile + 1] - r_begin;
@@ -352,7 +353,7 @@ interp_planned_short_quad_kernel(const int32_t *__restrict__ perm, const int32_t
     V *s_data = reinterpret_cast<V *>(lds_raw);                  // [n_r][4]
 
     const int64_t b = blockIdx.x;
-    const int64_t tile = (b & 7) * tiles_per_xcd + (b >> 3);
+    const int64_t tile = xcd_block(b, tiles_per_xcd);
     if (tile >= n_tiles) return;
     const int c_begin = tile_cell_begin[tile], n_c = tile_cell_begin[tile + 1] - c_begin;
     const int r_begin = tile_row_begin[tile], n_r = tile_row_begin[tile + 1] - r_begin;
@@ -1473,7 +1474,7 @@ __global__ void __launch_bounds__(256, 2)
 plan_loads_kernel(const int32_t *__restrict__ tile_row_begin, const int32_t *__restrict__ rows, const char *__restrict__ data,
                   uint64_t stride_bytes, uint64_t row_bytes, int n_lines, int64_t n_tiles, int64_t tiles_per_xcd, float *__restrict__ sink) {
     extern __shared__ float4 lds_raw[];
-    const int64_t tile = (int64_t)(blockIdx.x & 7) * tiles_per_xcd + (blockIdx.x >> 3);      // XCD-aware, tile order (run_map, one run per tile)
+    const int64_t tile = xcd_block(blockIdx.x, tiles_per_xcd);                               // XCD-aware, tile order (run_map, one run per tile)
     if (tile >= n_tiles) return;
     const int r_begin = tile_row_begin[tile], n_r = tile_row_begin[tile + 1] - r_begin;
     const int srow = threadIdx.x >> 3, svec = threadIdx.x & 7;

@@ -6,7 +6,7 @@
 // G lanes (G = 4..64, 8-16 vectors per lane) owns one row; each lane reads 16-byte vectors G vectors apart (a wavefront
 // instruction covers up to 1 KiB of contiguous memory) and works in f64 -- two passes over the up to
 // sixteen values it holds in registers -- and the lanes of the group combine their partial sums with xor-shuffles.
-#include "common.h"
+#include "typed_rows.h"
 
 #include <cmath>
 
@@ -22,14 +22,6 @@ __device__ __forceinline__ Moments merge(const Moments &a, const Moments &b) {
     const double n = a.n + b.n, delta = b.mean - a.mean;
     return Moments{n, a.mean + delta * (b.n / n), a.m2 + b.m2 + delta * delta * (a.n * b.n / n)};
 }
-
-template <typename T, int VEC>
-struct VecLoad;
-template <> struct VecLoad<float, 4> { using type = float4; };
-template <> struct VecLoad<float, 2> { using type = float2; };
-template <> struct VecLoad<float, 1> { using type = float; };
-template <> struct VecLoad<double, 2> { using type = double2; };
-template <> struct VecLoad<double, 1> { using type = double; };
 
 template <int G>
 __device__ __forceinline__ double group_sum(double v) {
@@ -48,7 +40,6 @@ template <typename T, int VEC, int G, bool ABS>
 __global__ void __launch_bounds__(256)
 row_moments_kernel(const T *__restrict__ data, int64_t n_rows, int64_t row_len, int64_t in_stride, int ddof,
                    double *__restrict__ mean_out, double *__restrict__ std_out) {
-    using V = typename VecLoad<T, VEC>::type;
     constexpr int ROWS = 256 / G;
     const int64_t row = (int64_t)blockIdx.x * ROWS + threadIdx.x / G;
     const int lane = threadIdx.x % G;
@@ -66,10 +57,11 @@ row_moments_kernel(const T *__restrict__ data, int64_t n_rows, int64_t row_len, 
         for (int u = 0; u < 4; ++u) {
             const int64_t v = base + lane + (int64_t)u * G;
             ok[u] = v < n_vec;
-            const V raw = *reinterpret_cast<const V *>(p + (ok[u] ? v : 0) * VEC);
-            const T *e = reinterpret_cast<const T *>(&raw);
+            row_load_wide<T, VEC>(p + (ok[u] ? v : 0) * VEC, x[u]);
+            if constexpr (ABS) {
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) x[u][i] = ABS ? fabs((double)e[i]) : (double)e[i];
+                for (int i = 0; i < VEC; ++i) x[u][i] = fabs(x[u][i]);
+            }
         }
         const bool last_chunk = base + (int64_t)G * 4 >= n_vec;
         const bool with_tail = last_chunk && lane == 0 && n_tail > 0;
@@ -143,18 +135,12 @@ static int row_moments_impl(const void *d_data, int dtype, int64_t n_rows, int64
     if (in_stride <= 0) in_stride = row_len;
     S3_REQUIRE(in_stride >= row_len, "s3_row_moments: in_stride %lld < row_len %lld", (long long)in_stride, (long long)row_len);
     hipStream_t st = as_stream(stream);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_data);
-#define S3_MOMENTS(T, VEC)                                                                                                        \
-    return absolute ? launch_moments<T, VEC, true>(d_data, n_rows, row_len, in_stride, ddof, d_mean, d_std, st)                   \
-                    : launch_moments<T, VEC, false>(d_data, n_rows, row_len, in_stride, ddof, d_mean, d_std, st)
-    if (dtype == S3_DTYPE_F32) {
-        if (in_stride % 4 == 0 && a % 16 == 0) S3_MOMENTS(float, 4);
-        if (in_stride % 2 == 0 && a % 8 == 0) S3_MOMENTS(float, 2);
-        S3_MOMENTS(float, 1);
-    }
-    if (in_stride % 2 == 0 && a % 16 == 0) S3_MOMENTS(double, 2);
-    S3_MOMENTS(double, 1);
-#undef S3_MOMENTS
+    return dispatch_rows<EveryRowWidth>(dtype, row_width<EveryRowWidth>(dtype, d_data, in_stride), [&](auto row) {
+        using T = typename decltype(row)::type;
+        constexpr int VEC = decltype(row)::vec;
+        return absolute ? launch_moments<T, VEC, true>(d_data, n_rows, row_len, in_stride, ddof, d_mean, d_std, st)
+                        : launch_moments<T, VEC, false>(d_data, n_rows, row_len, in_stride, ddof, d_mean, d_std, st);
+    });
 }
 
 extern "C" {

@@ -1,10 +1,10 @@
 // Operand staging of the f64 matrix-core kernels (v_mfma_f64_16x16x4_f64), shared by csrc/svd.hip (Gram matrix, tall GEMMs) and
-// csrc/spectral.hip (segment DFT): tile constants, the typed 16-byte piece loads, the transposed L tile of a tall product and the
-// MFMA step of a wavefront over one LDS buffer.  gfx950 only.
+// csrc/spectral.hip (segment DFT): tile constants, the 16-byte pieces of a panel (their vector type and the host's choice
+// of its width come from csrc/typed_rows.h), the transposed L tile of a tall product and the MFMA step of a wavefront over one LDS buffer.  gfx950 only.
 #ifndef S3_MFMA_STAGE_H
 #define S3_MFMA_STAGE_H
 
-#include "common.h"
+#include "typed_rows.h"
 
 namespace s3 {
 
@@ -21,7 +21,8 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 // two Gram matrices agree to the bit.  A 16-byte piece is PW = 2 doubles or 4 floats: 16 threads per row of a 16 x 128 panel take
 // 4 pieces at columns c0 + 32 p (double) or 2 pieces at c0 + 64 p (float), eight values per thread and panel either way.
 // VEC = elements per load instruction of a piece that lies inside the matrix: chosen per LAUNCH on the host from the alignment
-// every row start shares (stage_vec), never per lane; a piece across the matrix's edge is read element by element.
+// every row start shares (row_width<StagedRowWidths>: the base, the row pitch and, for the segments of spectral.hip, which start a
+// multiple of the hop into a row, the hop), never per lane; a piece across the matrix's edge is read element by element.
 // (T = double keeps the scalar form it always had: VEC = 1.)
 template <typename T> struct stage_traits;
 template <> struct stage_traits<double> { static constexpr int PW = 2; };
@@ -32,10 +33,9 @@ template <typename T, int VEC, int PW>
 __device__ __forceinline__ void load_piece(const T *__restrict__ p, int avail, double fill, double (&out)[PW]) {
     if constexpr (VEC > 1) {
         if (avail >= PW) {
-            typedef T vec_t __attribute__((ext_vector_type(VEC)));
 #pragma unroll
             for (int q = 0; q < PW; q += VEC) {
-                const vec_t v = *reinterpret_cast<const vec_t *>(p + q);
+                const RowVecNative<T, VEC> v = *reinterpret_cast<const RowVecNative<T, VEC> *>(p + q);
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) out[q + j] = (double)v[j];
             }
@@ -44,15 +44,6 @@ __device__ __forceinline__ void load_piece(const T *__restrict__ p, int avail, d
     }
 #pragma unroll
     for (int j = 0; j < PW; ++j) out[j] = j < avail ? (double)p[j] : fill;
-}
-
-// elements per load for float rows: every row start is (base + row * stride * 4) bytes, so the alignment all of them share is
-// the one of (base | stride * 4); a kernel that starts reading `step` elements into a row, or a multiple of it (the segments of
-// spectral.hip: step = hop), shares the alignment of (base | stride * 4 | step * 4)
-inline int stage_vec(const void *base, int64_t stride_elements, int64_t step_elements = 0) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(base) | (uintptr_t)(stride_elements * (int64_t)sizeof(float)) |
-                        (uintptr_t)(step_elements * (int64_t)sizeof(float));
-    return (a & 15) == 0 ? 4 : (a & 7) == 0 ? 2 : 1;
 }
 
 // L tile of a tall product, the role of thread (lrow = tid >> 1, lk = (tid & 1) * 8): ra[i] = lr[kk0 + i] - mu for the eight

@@ -11,14 +11,9 @@
 // Regime: the reverse of csrc/export.hip.  The table that is gathered from (the grid, Nc rows) is small and stays in L2 /
 // Infinity Cache; the targets (N points) are many and stream: per point 12*k bytes of weights / ids and one original row.
 //
-// Work split: a workgroup (256 threads) owns one REDUCTION BLOCK of S3_RECON_BLOCK consecutive points of the launch order.
-// Its threads form 256/LP point slots of LP lanes (LP = 4..64, the power of two that covers a row's VEC-wide pieces); a slot
-// takes every (256/LP)-th point of the block, its lane l the columns [(chunk*LP + l)*VEC, +VEC) of the row.  The block is
-// walked in STAGES of stage_pts points (64 unless LDS is short: recon_lds): the weights / ids of a whole stage are put into LDS
-// between one pair of barriers, then the slots sweep the stage in stage_pts / (256/LP) passes without a barrier.  Rows longer
-// than LP*VEC columns are swept in chunks (chunk loop outside, stage and point loops inside), so a lane's columns are fixed
-// while it walks its points and the column sums stay in registers; the price is that the block's tables are read from global
-// memory and staged once PER CHUNK (12*k*n_chunks bytes per point; one chunk up to 256 fp32 / 128 f64 columns).
+// Work split: the point slots of csrc/point_slots.h.  A workgroup owns one REDUCTION BLOCK of S3_RECON_BLOCK consecutive points
+// of the launch order; the staged tables are the weights and ids (12*k bytes per point and chunk; one chunk up to 256 fp32 /
+// 128 f64 columns).  A lane's columns are fixed while it walks its points, so the column sums stay in registers.
 //
 // Order of every floating-point sum (no atomics: same inputs, same bits):
 //   fitted value      f64 fma chain over the neighbours 0..k-1 (independent of row_len, VEC and LP)
@@ -26,7 +21,8 @@
 //                     the LP lanes), chunks merged with Chan's update: the scheme of row_moments_kernel (csrc/metric.hip)
 //   column sums       a lane adds its points in ascending order, the slots are added in ascending order, the blocks by
 //                     recon_reduce_kernel: 16 contiguous runs of blocks, each in ascending order, then the runs in order
-#include "common.h"
+#include "point_slots.h"
+#include "typed_rows.h"
 
 #include <cmath>
 
@@ -34,25 +30,9 @@ namespace s3 {
 
 namespace {
 
-constexpr int RECON_THREADS = 256;
+constexpr int RECON_THREADS = POINT_THREADS;
 constexpr int RECON_RUNS = 16;          // runs of blocks in the second pass
 constexpr int RECON_RCOLS = 16;         // columns per workgroup of the second pass
-
-template <typename T, int VEC>
-struct RVec;
-template <> struct RVec<float, 4> { using type = float4; };
-template <> struct RVec<float, 1> { using type = float; };
-template <> struct RVec<double, 2> { using type = double2; };
-template <> struct RVec<double, 1> { using type = double; };
-
-template <typename T, int VEC>
-__device__ __forceinline__ void rload(const T *__restrict__ p, double (&v)[VEC]) {
-    using V = typename RVec<T, VEC>::type;
-    const V raw = *reinterpret_cast<const V *>(p);
-    const T *e = reinterpret_cast<const T *>(&raw);
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) v[i] = (double)e[i];
-}
 
 __device__ __forceinline__ double slot_sum(double v, int lp) {
     for (int off = lp >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off);     // xor butterfly inside the aligned group of lp lanes
@@ -97,10 +77,7 @@ recon_kernel(const double *__restrict__ w, const int32_t *__restrict__ idx, int6
     double *s_w = s_mom + (n_chunks > 1 ? 2 * S3_RECON_BLOCK : 0);              // [stage_pts*k]
     int32_t *s_idx = reinterpret_cast<int32_t *>(s_w + (size_t)stage_pts * k);  // [stage_pts*k]
 
-    // consecutive blocks of the spatial order gather the same grid rows: workgroups that share blockIdx % 8 share an XCD's L2,
-    // so each of them walks one contiguous eighth of the blocks (speed only)
-    const int64_t b = blockIdx.x;
-    const int64_t blk = (b & 7) * blocks_per_xcd + (b >> 3);
+    const int64_t blk = xcd_block(blockIdx.x, blocks_per_xcd);
     if (blk >= n_blocks) return;
     const int64_t p0 = blk * S3_RECON_BLOCK;
     const int n_p = (int)min((int64_t)S3_RECON_BLOCK, n - p0);
@@ -147,7 +124,7 @@ recon_kernel(const double *__restrict__ w, const int32_t *__restrict__ idx, int6
                 for (; m + 8 <= k; m += 8) {
                     double v[8][VEC];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) rload<TG, VEC>(col + (int64_t)ip[m + u] * row_len, v[u]);
+                    for (int u = 0; u < 8; ++u) row_load_wide<TG, VEC>(col + (int64_t)ip[m + u] * row_len, v[u]);
 #pragma unroll
                     for (int u = 0; u < 8; ++u) {
                         const double wu = wp[m + u];
@@ -157,15 +134,15 @@ recon_kernel(const double *__restrict__ w, const int32_t *__restrict__ idx, int6
                 }
                 for (; m + 2 <= k; m += 2) {
                     double v0[VEC], v1[VEC];
-                    rload<TG, VEC>(col + (int64_t)ip[m] * row_len, v0);
-                    rload<TG, VEC>(col + (int64_t)ip[m + 1] * row_len, v1);
+                    row_load_wide<TG, VEC>(col + (int64_t)ip[m] * row_len, v0);
+                    row_load_wide<TG, VEC>(col + (int64_t)ip[m + 1] * row_len, v1);
                     const double w0 = wp[m], w1 = wp[m + 1];
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) acc[i] = fma(w1, v1[i], fma(w0, v0[i], acc[i]));
                 }
                 for (; m < k; ++m) {
                     double v0[VEC];
-                    rload<TG, VEC>(col + (int64_t)ip[m] * row_len, v0);
+                    row_load_wide<TG, VEC>(col + (int64_t)ip[m] * row_len, v0);
                     const double w0 = wp[m];
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) acc[i] = fma(w0, v0[i], acc[i]);
@@ -268,43 +245,23 @@ recon_reduce_kernel(const double *__restrict__ partial, int64_t n_blocks, int64_
 
 int64_t recon_blocks(int64_t n) { return (n + S3_RECON_BLOCK - 1) / S3_RECON_BLOCK; }
 
-// LDS of a launch with `lanes` lanes per point slot: the column scratch, the moments of rows of several chunks, and the weights /
-// ids of one STAGE of points -- up to 64 points (19.5 KB at k = 26), halved while the total exceeds RECON_LDS_MAX, never fewer
-// than one pass of the slots (256 / lanes points)
-constexpr size_t RECON_LDS_MAX = 48 * 1024;
-struct ReconLds { int stage_pts; size_t bytes; };
-ReconLds recon_lds(int64_t pieces, int lanes, int k, int vec) {
-    const int64_t chunks = (pieces + lanes - 1) / lanes;
-    const size_t fixed = sizeof(double) * (2 * vec * RECON_THREADS + (chunks > 1 ? 2 * S3_RECON_BLOCK : 0));
-    const size_t per_point = (size_t)k * (sizeof(double) + sizeof(int32_t));
-    int stage_pts = 64;
-    while (stage_pts > RECON_THREADS / lanes && fixed + stage_pts * per_point > RECON_LDS_MAX) stage_pts /= 2;
-    return ReconLds{stage_pts, fixed + stage_pts * per_point};
-}
-
 template <typename TG, typename TO, int VEC>
 int launch_recon(const double *w, const int32_t *idx, int64_t n, int k, const void *grid, int64_t row_len, const void *orig,
                  int64_t orig_stride, const int32_t *rows, const double *scale, double *mean, double *m2, double *colsum,
                  double *partial, hipStream_t st) {
-    const int64_t pieces = row_len / VEC;
-    int lp = 4;                                             // at least 4 lanes per point: at most 64 points' tables in LDS
-    while (lp < 64 && lp < pieces) lp *= 2;
-    ReconLds shape = recon_lds(pieces, lp, k, VEC);
-    while (lp < 64 && shape.bytes > RECON_LDS_MAX) {        // (short rows with many neighbours: fewer, wider slots)
-        lp *= 2;
-        shape = recon_lds(pieces, lp, k, VEC);
-    }
-    const int64_t n_chunks = (pieces + lp - 1) / lp;
-    S3_REQUIRE(n_chunks < ((int64_t)1 << 20), "s3_recon_error: row_len %lld too long", (long long)row_len);
-    const size_t lds = shape.bytes;
-    const int stage_pts = shape.stage_pts;
-    S3_REQUIRE(lds <= RECON_LDS_MAX, "s3_recon_error: %zu bytes of LDS needed", lds);
+    // LDS (slot_shape, csrc/point_slots.h): the column scratch, the moments of rows of several chunks, and per point of a stage its
+    // weights and ids (64 points: 19.5 KB at k = 26)
+    const size_t scratch = sizeof(double) * 2 * VEC * RECON_THREADS, moments = sizeof(double) * 2 * S3_RECON_BLOCK;
+    SlotShape shape;
+    if (const int rc = slot_shape("s3_recon_error", row_len, row_len / VEC, (size_t)k * (sizeof(double) + sizeof(int32_t)), scratch,
+                                  scratch + moments, shape))
+        return rc;
     const int64_t n_blocks = recon_blocks(n);
-    const int64_t blocks_per_xcd = (n_blocks + 7) / 8;
-    S3_REQUIRE(blocks_per_xcd * 8 < ((int64_t)1 << 31), "s3_recon_error: too many points");
-    recon_kernel<TG, TO, VEC><<<(unsigned)(blocks_per_xcd * 8), RECON_THREADS, lds, st>>>(
+    const XcdGrid xcd = xcd_grid(n_blocks);
+    S3_REQUIRE(xcd.fits(), "s3_recon_error: too many points");
+    recon_kernel<TG, TO, VEC><<<(unsigned)xcd.grid, RECON_THREADS, shape.lds_bytes, st>>>(
         w, idx, n, k, static_cast<const TG *>(grid), row_len, static_cast<const TO *>(orig), orig_stride, rows, scale, mean, m2,
-        partial, lp, stage_pts, (int)n_chunks, n_blocks, blocks_per_xcd);
+        partial, shape.lanes, shape.stage_pts, (int)shape.n_chunks, n_blocks, xcd.per_xcd);
     S3_LAUNCH_CHECK();
     const int64_t n_cols = 2 * row_len;
     recon_reduce_kernel<<<(unsigned)((n_cols + RECON_RCOLS - 1) / RECON_RCOLS), RECON_THREADS, 0, st>>>(partial, n_blocks, n_cols,
@@ -356,26 +313,13 @@ int s3_recon_error(const double *d_w, const int32_t *d_idx, int64_t n, int k, co
     }
     S3_REQUIRE(d_w && d_idx && d_grid && d_orig && d_mean && d_m2 && d_scratch, "s3_recon_error: null array");
     double *partial = static_cast<double *>(d_scratch);
-    const uintptr_t a_grid = reinterpret_cast<uintptr_t>(d_grid);
-#define S3_RECON(TG, TO, VEC)                                                                                                    \
-    return launch_recon<TG, TO, VEC>(d_w, d_idx, n, k, d_grid, row_len, d_orig, orig_stride, d_rows, d_scale, d_mean, d_m2, d_colsum, \
-                                     partial, st)
     // the width of a lane's piece follows the GRID rows (k reads per element; the original row is read once, by elements)
-    if (grid_dtype == S3_DTYPE_F32) {
-        if (row_len % 4 == 0 && a_grid % 16 == 0) {
-            if (orig_dtype == S3_DTYPE_F32) S3_RECON(float, float, 4);
-            S3_RECON(float, double, 4);
-        }
-        if (orig_dtype == S3_DTYPE_F32) S3_RECON(float, float, 1);
-        S3_RECON(float, double, 1);
-    }
-    if (row_len % 2 == 0 && a_grid % 16 == 0) {
-        if (orig_dtype == S3_DTYPE_F32) S3_RECON(double, float, 2);
-        S3_RECON(double, double, 2);
-    }
-    if (orig_dtype == S3_DTYPE_F32) S3_RECON(double, float, 1);
-    S3_RECON(double, double, 1);
-#undef S3_RECON
+    return dispatch_rows<WidestRowWidth>(grid_dtype, row_width<WidestRowWidth>(grid_dtype, d_grid, row_len), [&](auto g) {
+        return dispatch_rows<ScalarRows>(orig_dtype, 1, [&](auto o) {
+            return launch_recon<typename decltype(g)::type, typename decltype(o)::type, decltype(g)::vec>(
+                d_w, d_idx, n, k, d_grid, row_len, d_orig, orig_stride, d_rows, d_scale, d_mean, d_m2, d_colsum, partial, st);
+        });
+    });
 }
 
 }  // extern "C"

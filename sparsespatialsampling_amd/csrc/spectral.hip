@@ -152,18 +152,13 @@ static int segments_run(const char *who, const void *d_x, int dtype, int64_t n_r
     const int64_t gx = (n_rows + GB - 1) / GB, gy = (n_f + SF - 1) / SF;
     S3_REQUIRE(gx < ((int64_t)1 << 31) && gy <= 65535, "%s: shape too large for one launch", who);
     hipStream_t st = as_stream(stream);
-    if (dtype == S3_DTYPE_F64) {
-        launch_segments<double, 1>(static_cast<const double *>(d_x), n_rows, in_stride, d_mean, (int)nperseg, hop, (int)n_blk, d_bre, d_bim,
-                                   (int)n_f, d_scale, d_out, st);
-    } else {
-        // a segment starts b * hop elements into its row: an odd hop breaks the 16-byte alignment even where the rows are aligned
-        const float *xf = static_cast<const float *>(d_x);
-        switch (stage_vec(d_x, in_stride, n_blk > 1 ? hop : 0)) {
-        case 4: launch_segments<float, 4>(xf, n_rows, in_stride, d_mean, (int)nperseg, hop, (int)n_blk, d_bre, d_bim, (int)n_f, d_scale, d_out, st); break;
-        case 2: launch_segments<float, 2>(xf, n_rows, in_stride, d_mean, (int)nperseg, hop, (int)n_blk, d_bre, d_bim, (int)n_f, d_scale, d_out, st); break;
-        default: launch_segments<float, 1>(xf, n_rows, in_stride, d_mean, (int)nperseg, hop, (int)n_blk, d_bre, d_bim, (int)n_f, d_scale, d_out, st); break;
-        }
-    }
+    // a segment starts b * hop elements into its row: an odd hop breaks the 16-byte alignment even where the rows are aligned
+    const int width = row_width<StagedRowWidths>(dtype, d_x, in_stride, n_blk > 1 ? hop : 0);
+    dispatch_rows<StagedRowWidths>(dtype, width, [&](auto row) {
+        using T = typename decltype(row)::type;
+        launch_segments<T, decltype(row)::vec>(static_cast<const T *>(d_x), n_rows, in_stride, d_mean, (int)nperseg, hop, (int)n_blk, d_bre, d_bim,
+                                               (int)n_f, d_scale, d_out, st);
+    });
     S3_LAUNCH_CHECK();
     return S3_OK;
 }

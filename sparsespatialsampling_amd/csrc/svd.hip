@@ -14,7 +14,7 @@
 // owns a 64 x 64 quarter = 4 x 4 MFMA tiles (128 accumulator VGPRs) and issues 16 MFMAs per 4 rows.  The row slices'
 // partial blocks (cut to the part that lies inside G: a T of 130 keeps 128 x 128 + 128 x 2 + 2 x 2 values per slice, not three
 // 128 x 128 blocks) are added in slice order by a second kernel (deterministic), which also mirrors the lower triangle.
-#include "mfma_stage.h"        // tile constants, load_piece, stage_vec, the L tile and the MFMA step (shared with spectral.hip)
+#include "mfma_stage.h"        // tile constants, load_piece, the L tile and the MFMA step (shared with spectral.hip)
 
 #include <algorithm>
 #include <vector>
@@ -249,16 +249,10 @@ static int gemm_run(const char *who, const void *d_l, int dtype, int64_t m, int6
     const int64_t gx = (m + GB - 1) / GB, gy = (n + (n <= 64 ? 64 : GB) - 1) / (n <= 64 ? 64 : GB);
     S3_REQUIRE(gx < ((int64_t)1 << 31) && gy <= 65535, "%s: shape too large for one launch", who);
     hipStream_t st = as_stream(stream);
-    if (dtype == S3_DTYPE_F64) {
-        launch_gemm<double, 1>(static_cast<const double *>(d_l), m, (int)k, l_stride, d_lmean, d_b, (int)n, d_e, e_stride, d_emean, d_c, st);
-    } else {
-        const float *lf = static_cast<const float *>(d_l);
-        switch (stage_vec(d_l, l_stride)) {
-        case 4: launch_gemm<float, 4>(lf, m, (int)k, l_stride, d_lmean, d_b, (int)n, d_e, e_stride, d_emean, d_c, st); break;
-        case 2: launch_gemm<float, 2>(lf, m, (int)k, l_stride, d_lmean, d_b, (int)n, d_e, e_stride, d_emean, d_c, st); break;
-        default: launch_gemm<float, 1>(lf, m, (int)k, l_stride, d_lmean, d_b, (int)n, d_e, e_stride, d_emean, d_c, st); break;
-        }
-    }
+    dispatch_rows<StagedRowWidths>(dtype, row_width<StagedRowWidths>(dtype, d_l, l_stride), [&](auto row) {
+        using T = typename decltype(row)::type;
+        launch_gemm<T, decltype(row)::vec>(static_cast<const T *>(d_l), m, (int)k, l_stride, d_lmean, d_b, (int)n, d_e, e_stride, d_emean, d_c, st);
+    });
     S3_LAUNCH_CHECK();
     return S3_OK;
 }
@@ -318,17 +312,11 @@ static int gram_run(const char *who, const void *d_x, int dtype, int64_t n_rows,
     S3_HIP_CHECK(hipMemcpyAsync(d_offs, offs.data(), sizeof(int64_t) * offs.size(), hipMemcpyHostToDevice, st));
     S3_HIP_CHECK(hipStreamSynchronize(st));               // `pairs` and `offs` are locals
     const dim3 grid((unsigned)n_pairs, (unsigned)slices);
-    if (dtype == S3_DTYPE_F64) {
-        gram_block_kernel<double, 1><<<grid, 256, 0, st>>>(static_cast<const double *>(d_x), n_rows, (int)t, in_stride, d_mean, d_weight, d_pairs,
-                                                          d_offs, rows_per_slice, d_partial);
-    } else {
-        const float *xf = static_cast<const float *>(d_x);
-        switch (stage_vec(d_x, in_stride)) {
-        case 4: gram_block_kernel<float, 4><<<grid, 256, 0, st>>>(xf, n_rows, (int)t, in_stride, d_mean, d_weight, d_pairs, d_offs, rows_per_slice, d_partial); break;
-        case 2: gram_block_kernel<float, 2><<<grid, 256, 0, st>>>(xf, n_rows, (int)t, in_stride, d_mean, d_weight, d_pairs, d_offs, rows_per_slice, d_partial); break;
-        default: gram_block_kernel<float, 1><<<grid, 256, 0, st>>>(xf, n_rows, (int)t, in_stride, d_mean, d_weight, d_pairs, d_offs, rows_per_slice, d_partial); break;
-        }
-    }
+    dispatch_rows<StagedRowWidths>(dtype, row_width<StagedRowWidths>(dtype, d_x, in_stride), [&](auto row) {
+        using T = typename decltype(row)::type;
+        gram_block_kernel<T, decltype(row)::vec><<<grid, 256, 0, st>>>(static_cast<const T *>(d_x), n_rows, (int)t, in_stride, d_mean, d_weight, d_pairs,
+                                                                      d_offs, rows_per_slice, d_partial);
+    });
     S3_LAUNCH_CHECK();
     gram_reduce_kernel<<<dim3((unsigned)n_pairs, GB * GB / 256), 256, 0, st>>>(d_partial, d_pairs, d_offs, n_pairs, (int)slices, (int)t, d_gram);
     S3_LAUNCH_CHECK();
