@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 13
+#define S3_ABI_VERSION 14
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -398,6 +398,56 @@ int s3_grad_coeff(const double *d_pts /*[n,dim]*/, int64_t n, int dim, const int
 int s3_grad_apply(const double *d_coef /*[n,k,dim]*/, const int32_t *d_idx /*[n,k]*/, int64_t n, int k, int dim, const void *d_field,
                   int dtype, int n_comp, int64_t row_len, int64_t in_stride, const int32_t *d_rows /*[n] or NULL*/, int mode,
                   double *d_out, int64_t out_stride, s3_stream stream);
+
+/* ---- sampling a grid field at arbitrary positions by exact cell location (csrc/sample.hip; no counterpart in the reference) ----
+ * A generated grid is a set of disjoint axis-aligned dyadic boxes: cell j has the centre c_j [dim] (dim 2 | 3), the level l_j and the
+ * edge h(l_j) = width / 2^l_j, `width` being the size of the initial cell.  The root's position is not an input (S^3 files do not
+ * store it); a lattice is derived instead.  With L = max l, lmin = min l, h_min = h(L), H = h(lmin), per axis and in plain f64:
+ *     corner = c_j - H/2 for the first cell j of level lmin        lo = min over the cells of c - h/2
+ *     origin = corner - ceil((corner - lo)/H - 1e-9) * H
+ *     a      = rint(((c - h/2) - origin) / h_min)                  the anchor of a leaf: an integer vector, a multiple of 2^(L-l)
+ *     key(i) = bit b of i[axis] at position b*dim + axis           the leaf owns the keys [key(a), key(a) + 2^(dim (L-l)))
+ * s3_cell_index computes the keys on the device, sorts (key, cell) with s3_sort_pairs and checks that the sorted ranges are
+ * disjoint.  It writes the sorted range starts, ends and cell ids (d_starts, d_ends, d_ids: n entries each) and the lattice
+ * (h_origin[3], *h_hmin, *h_depth = L) and returns when they are complete.  A grid is REFUSED with S3_EINVAL, the counts in
+ * h_refused[4]: [0] cells with an anchor more than 1e-6 lattice units off an integer or outside [0, 2^L), [1] cells whose anchor is
+ * no multiple of 2^(L-l), [2] sorted ranges that reach into their successor, [3] dim * L where that exceeds 63.  2:1 balance is
+ * not assumed.
+ *
+ * s3_cell_locate, one query per thread: i = floor((x - origin)/h_min) per axis (half-open: a point on a face belongs to the upper
+ * cell), binary search of key(i) over the sorted starts, range test.  d_out[q] (int32, one entry per point, caller's cell
+ * numbering) = the cell that holds point q, or -1 where no leaf does: outside the domain, inside a body, NaN or infinite
+ * coordinates (tested before the conversion to an integer).  Thread j takes point d_rows[j] (d_rows NULL: point j; launch the
+ * points in the order of s3_spatial_order).
+ *
+ * s3_cell_sample, one launch per snapshot batch: d_field rows [n_comp][row_len] f32 or f64 (dtype: S3_DTYPE_*) with pitch in_stride
+ * ELEMENTS (0 = n_comp * row_len), read where they lie; n_comp is 1, 2 or 3 per launch (a wider field goes in groups: offset d_field
+ * and d_out, keep the pitches).  Row q of d_out (f64, pitch out_stride elements, 0 = n_comp * row_len) receives [n_comp][row_len]
+ * for point q = d_rows[j] (d_rows NULL: q = j) with id = d_cell[q]:
+ *     S3_SAMPLE_CELL    (double) field[id]: a bit-exact copy; n_field_rows = rows of the field (cells).  dim, d_points, d_centers,
+ *                       d_levels, d_faces, n_cells and width are not read.
+ *     S3_SAMPLE_LINEAR  the field lives on the grid NODES (n_field_rows of them), d_faces [n_cells][2^dim] lists the corners of a
+ *                       cell in the order (-,-), (-,+), (+,+), (+,-) in 2-D and that order at z+, then at z-, in 3-D:
+ *                           xi_a = clamp((x_a - (c_a - h/2)) / h, 0, 1)                                    in f64, as written
+ *                           w_m  = prod_a (s_ma > 0 ? xi_a : 1 - xi_a), evaluated as t = (s_m0 > 0 ? xi_0 : 1 - xi_0), then
+ *                                  t = s_ma > 0 ? t * xi_a : fma(-xi_a, t, t) for a = 1 .. dim-1           one rounding per axis
+ *                           out  = sum_m w_m f[faces[id][m]]                  f64 fma chain over m = 0 .. 2^dim - 1 from 0
+ *                       The weights are formed in the kernel; nothing of size [nq][2^dim] is stored.
+ * In both modes a row with id outside [0, n_cells) (-1: no cell) or with a corner outside [0, n_field_rows) is NaN in every column.
+ * No floating-point atomics: the same inputs give the same bits on every run, whatever row_len and n_comp. */
+#define S3_SAMPLE_CELL 0
+#define S3_SAMPLE_LINEAR 1
+int s3_cell_index(const double *d_centers /*[n,dim]*/, const int32_t *d_levels /*[n]*/, int64_t n, int dim, double width,
+                  uint64_t *d_starts /*[n]*/, uint64_t *d_ends /*[n]*/, int32_t *d_ids /*[n]*/, double *h_origin /*[3]*/,
+                  double *h_hmin, int *h_depth, int64_t *h_refused /*[4]*/, s3_stream stream);
+int s3_cell_locate(const uint64_t *d_starts, const uint64_t *d_ends, const int32_t *d_ids, int64_t n_cells, int dim, int depth,
+                   const double *h_origin /*[3]*/, double h_min, const double *d_points /*[nq,dim]*/, int64_t nq,
+                   const int32_t *d_rows /*[nq] or NULL*/, int32_t *d_out /*[nq]*/, s3_stream stream);
+int s3_cell_sample(int mode, const int32_t *d_cell /*[nq]*/, int64_t nq, const int32_t *d_rows /*[nq] or NULL*/, const void *d_field,
+                   int dtype, int n_comp, int64_t row_len, int64_t in_stride, int64_t n_field_rows, int dim,
+                   const double *d_points /*[nq,dim]*/, const double *d_centers /*[n_cells,dim]*/, const int32_t *d_levels /*[n_cells]*/,
+                   double width, const int32_t *d_faces /*[n_cells,2^dim]*/, int64_t n_cells, double *d_out, int64_t out_stride,
+                   s3_stream stream);
 
 /* ---- yardsticks of the measurement (bench.py's roofline line; no counterpart in the reference, not on any product path) ----
  * s3_yard_stream      a hand-written streaming kernel over d_src: every lane reads `reads` 16-byte vectors (coalesced) and

@@ -20,7 +20,7 @@ if _os.environ.get("S3_KEEP_RUNTIME_PINNING") != "1":
 
 from .version import __version__
 
-__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "__version__"]
+__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "Probe", "__version__"]
 
 
 def __getattr__(name):
@@ -37,4 +37,7 @@ def __getattr__(name):
     if name == "Gradient":
         from . import differential
         return differential.Gradient
+    if name == "Probe":
+        from . import sampling
+        return sampling.Probe
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -316,6 +316,137 @@ def grad_apply(coef, idx, field, mode, rows=None, out=None):
     return out
 
 
+SAMPLE_MODES = {"cell": 0, "linear": 1}     # S3_SAMPLE_* (s3hip.h)
+
+
+class CellIndex:
+    """what ``cell_index`` made of a grid: the sorted Morton ranges of its leaves (``starts`` / ``ends`` int64 holding the unsigned
+    keys, ``ids`` int32: the cell of each range), the lattice they live on (``origin`` float64 [3] on the host, ``h_min``,
+    ``depth``) and the grid itself (``centers`` f64 [n, dim], ``levels`` int32 [n], ``width``), all arrays on the device"""
+
+    def __init__(self, centers, levels, width, starts, ends, ids, origin, h_min, depth):
+        self.centers, self.levels, self.width = centers, levels, float(width)
+        self.starts, self.ends, self.ids = starts, ends, ids
+        self.origin, self.h_min, self.depth = origin, float(h_min), int(depth)
+        self.n_cells, self.dim = int(centers.shape[0]), int(centers.shape[1])
+
+
+def cell_index(centers, levels, width):
+    """the cell index of a generated grid (s3_cell_index): ``centers`` float64 [n, 2 | 3] and ``levels`` int32 / int64 [n] or [n, 1]
+    on the device, ``width`` the size of the initial cell.  -> ``CellIndex``.  ``ValueError`` with the counts where the grid is no
+    set of disjoint dyadic boxes on one lattice: cells off the lattice, misaligned cells, overlapping cells, or more than 63 key
+    bits (dim * max level)."""
+    if not (isinstance(centers, pt.Tensor) and centers.is_cuda and centers.dtype == pt.float64 and centers.dim() == 2
+            and int(centers.shape[1]) in (2, 3)):
+        raise TypeError("cell_index: centers must be a float64 device tensor [n, 2 | 3]")
+    n, dim = int(centers.shape[0]), int(centers.shape[1])
+    if not (isinstance(levels, pt.Tensor) and levels.is_cuda and levels.dtype in (pt.int32, pt.int64) and levels.numel() == n):
+        raise TypeError(f"cell_index: levels must be an int32 / int64 device tensor with {n} entries")
+    if n < 1:
+        raise ValueError("cell_index: a grid without cells")
+    width = float(width)
+    if not (width > 0.0 and np.isfinite(width)):
+        raise ValueError(f"cell_index: width must be a positive size, got {width!r}")
+    centers = centers.contiguous()
+    levels = levels.reshape(n).to(pt.int32).contiguous()
+    starts = pt.empty(n, dtype=pt.int64, device=centers.device)
+    ends, ids = pt.empty_like(starts), pt.empty(n, dtype=pt.int32, device=centers.device)
+    origin, refused = np.zeros(3, dtype=np.float64), np.zeros(4, dtype=np.int64)
+    h_min, depth = C.c_double(0.0), C.c_int(0)
+    lib = _lib.hip_lib()
+    rc = lib.s3_cell_index(_ptr(centers), _ptr(levels), n, dim, width, _ptr(starts), _ptr(ends), _ptr(ids), C.c_void_p(origin.ctypes.data),
+                           C.byref(h_min), C.byref(depth), C.c_void_p(refused.ctypes.data), _stream())
+    if rc == -1 and refused.any():
+        raise ValueError(f"cell_index: the grid of {n} cells is refused: " + lib.s3_last_error().decode(errors="replace")
+                         + f" (off the lattice {refused[0]}, misaligned {refused[1]}, overlapping {refused[2]}, key bits {refused[3]})")
+    check(rc, "s3_cell_index")
+    return CellIndex(centers, levels, width, starts, ends, ids, origin, h_min.value, depth.value)
+
+
+def _query_points(points, dim, who):
+    if not (isinstance(points, pt.Tensor) and points.is_cuda and points.dtype == pt.float64 and points.dim() == 2
+            and int(points.shape[1]) == dim and points.is_contiguous()):
+        raise TypeError(f"{who}: points must be a contiguous float64 device tensor [nq, {dim}]")
+    return int(points.shape[0])
+
+
+def cell_locate(index, points, rows=None, out=None):
+    """the cell that holds each point (s3_cell_locate): ``points`` float64 [nq, dim] on the device -> int32 [nq] in the caller's
+    cell numbering, -1 where no cell holds the point (outside the domain, inside a body, NaN / infinite coordinates).  A point on
+    a face belongs to the upper cell.  ``rows`` int32 [nq]: the order in which the points are launched (``spatial_order``)."""
+    if not isinstance(index, CellIndex):
+        raise TypeError("cell_locate: index must be what cell_index returned")
+    nq = _query_points(points, index.dim, "cell_locate")
+    if rows is not None and not (rows.is_cuda and rows.dtype == pt.int32 and rows.numel() == nq and rows.is_contiguous()):
+        raise TypeError(f"cell_locate: rows must be a contiguous int32 device tensor [{nq}]")
+    if out is None:
+        out = pt.empty(nq, dtype=pt.int32, device=points.device)
+    elif not (out.is_cuda and out.dtype == pt.int32 and out.numel() == nq and out.is_contiguous()):
+        raise TypeError(f"cell_locate: out must be a contiguous int32 device tensor [{nq}]")
+    check(_lib.hip_lib().s3_cell_locate(_ptr(index.starts), _ptr(index.ends), _ptr(index.ids), index.n_cells, index.dim, index.depth,
+                                        C.c_void_p(index.origin.ctypes.data), index.h_min, _ptr(points), nq, _ptr(rows), _ptr(out),
+                                        _stream()), "s3_cell_locate")
+    return out
+
+
+def cell_sample(ids, field, mode="cell", rows=None, out=None, index=None, points=None, faces=None):
+    """the field at located points (s3_cell_sample).  ``ids`` int32 [nq] as ``cell_locate`` returned them; ``field`` float32 / float64
+    on the device: [rows] (one snapshot), [rows, T] (rows may be pitched: read where they lie) or [rows, n_comp, T] contiguous.
+    -> f64 [nq, n_comp, T], written into ``out`` when given; rows with id -1 are NaN.
+
+    ``mode="cell"``: the field has one row per cell, the result is a bit-exact copy of the row of the containing cell.
+    ``mode="linear"``: the field has one row per grid NODE; ``index`` (the ``CellIndex``), ``points`` float64 [nq, dim] and
+    ``faces`` int32 [n_cells, 2^dim] (the corner nodes of every cell) are required, the result is the multilinear blend of the
+    containing cell's corner values.  ``rows`` int32 [nq]: the launch order.  The kernel takes up to three components per launch:
+    a wider field goes in groups."""
+    if mode not in SAMPLE_MODES:
+        raise ValueError(f"cell_sample: unknown mode {mode!r}, expected one of {sorted(SAMPLE_MODES)}")
+    if not (isinstance(ids, pt.Tensor) and ids.is_cuda and ids.dtype == pt.int32 and ids.dim() == 1 and ids.is_contiguous()):
+        raise TypeError("cell_sample: ids must be a contiguous int32 device tensor [nq]")
+    nq = int(ids.numel())
+    if not (isinstance(field, pt.Tensor) and field.is_cuda and field.dtype in DTYPE_CODE and 1 <= field.dim() <= 3):
+        raise TypeError("cell_sample: float32 / float64 device field [rows], [rows, T] or [rows, n_comp, T] required")
+    if field.dim() == 3:
+        n_comp, t = int(field.shape[1]), int(field.shape[2])
+        if not field.is_contiguous():
+            raise TypeError("cell_sample: a field [rows, n_comp, T] must be contiguous")
+        in_stride = n_comp * t
+    else:
+        n_comp = 1
+        t, in_stride = _pitched_rows(field, "cell_sample(field)")
+    n_rows = int(field.shape[0])
+    if t < 1 or n_comp < 1 or n_rows < 1:
+        raise ValueError(f"cell_sample: empty field {tuple(field.shape)}")
+    if rows is not None and not (rows.is_cuda and rows.dtype == pt.int32 and rows.numel() == nq and rows.is_contiguous()):
+        raise TypeError(f"cell_sample: rows must be a contiguous int32 device tensor [{nq}]")
+    dim, n_cells, width, centers, levels = 0, 0, 0.0, None, None
+    if mode == "linear":
+        if index is None or points is None or faces is None:
+            raise ValueError("cell_sample: mode 'linear' needs index, points and faces")
+        if not isinstance(index, CellIndex):
+            raise TypeError("cell_sample: index must be what cell_index returned")
+        dim, n_cells, width, centers, levels = index.dim, index.n_cells, index.width, index.centers, index.levels
+        if _query_points(points, dim, "cell_sample") != nq:
+            raise ValueError(f"cell_sample: {int(points.shape[0])} points for {nq} ids")
+        if not (isinstance(faces, pt.Tensor) and faces.is_cuda and faces.dtype == pt.int32 and faces.is_contiguous()
+                and tuple(faces.shape) == (n_cells, 1 << dim)):
+            raise TypeError(f"cell_sample: faces must be a contiguous int32 device tensor [{n_cells}, {1 << dim}]")
+    else:
+        points = faces = None
+    if out is None:
+        out = pt.empty((nq, n_comp, t), dtype=pt.float64, device=field.device)
+    elif not (isinstance(out, pt.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == pt.float64
+              and out.numel() == nq * n_comp * t and out.device == field.device):
+        raise TypeError(f"cell_sample: out must be a contiguous float64 device tensor of {nq} x {n_comp} x {t} values")
+    lib, item = _lib.hip_lib(), field.element_size()
+    for c0 in range(0, n_comp, 3):
+        group = min(3, n_comp - c0)
+        check(lib.s3_cell_sample(SAMPLE_MODES[mode], _ptr(ids), nq, _ptr(rows), C.c_void_p(field.data_ptr() + c0 * t * item),
+                                 DTYPE_CODE[field.dtype], group, t, in_stride, n_rows, dim, _ptr(points), _ptr(centers), _ptr(levels), width,
+                                 _ptr(faces), n_cells, C.c_void_p(out.data_ptr() + c0 * t * 8), n_comp * t, _stream()), "s3_cell_sample")
+    return out
+
+
 def _pitched_matrix(t, who):
     """row pitch in elements of a 2-D f32 / f64 device matrix with unit inner stride, read where it lies"""
     if not (t.is_cuda and t.dtype in DTYPE_CODE and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):

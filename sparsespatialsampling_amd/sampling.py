@@ -1,0 +1,185 @@
+"""
+Sampling of fields on a generated grid at arbitrary positions: probe points, lines, planes, rasters.  The reference has nothing of
+the kind: its post-processing hands the cell centres to a plotting library as a bare point cloud.
+
+A generated grid is a set of disjoint axis-aligned boxes, each a dyadic fraction of the initial cell, so "which cell holds this
+point" has exactly one answer -- and it is NOT the cell with the nearest centre wherever the level changes.  ``Probe`` answers it
+exactly (``hipops.cell_index``: Morton ranges of the leaves on a lattice derived from the grid, sorted once; ``hipops.cell_locate``:
+one binary search per point; a point on a face belongs to the upper cell) and then reads fields there (``hipops.cell_sample``,
+csrc/sample.hip), batch by batch:
+
+    mode="cell"     the value of the containing cell, a bit-exact copy: a slice shows the grid as it is
+    mode="linear"   for fields on the grid NODES (``interpolate_at_vertices=True`` exports): the multilinear blend of the containing
+                    cell's corner values, continuous inside a cell and across faces between cells of one level
+
+Points that no cell holds -- outside the domain or inside a body -- come back as NaN (``Probe.inside`` tells them apart), so a
+raster can go to ``imshow`` as it is.  ``line``, ``plane`` and ``raster`` only build point sets on the host.
+
+    probe = Probe.from_dataloader(loader, raster(lo, hi, (ny, nx)))
+    frames = hipops.snapshot_major(probe.sample(field), 1, n_snapshots)         # [T, ny * nx]
+"""
+import numpy as np
+import torch as pt
+
+from . import hipops
+
+
+def _as_tensor(x, what):
+    if isinstance(x, np.ndarray):
+        return pt.from_numpy(np.ascontiguousarray(x))
+    if not isinstance(x, pt.Tensor):
+        raise TypeError(f"{what} must be a numpy array or a torch tensor, got {type(x).__name__}")
+    return x
+
+
+# ---- point sets (host only) -------------------------------------------------------------------------------------------------
+def _vector(v, what, dim=None):
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    if v.size not in ((2, 3) if dim is None else (dim,)):
+        raise ValueError(f"{what} must have {'2 or 3' if dim is None else dim} components, got {v.size}")
+    return v
+
+
+def _shape(shape, n_axes=None):
+    shape = (int(shape),) if np.isscalar(shape) else tuple(int(s) for s in shape)
+    if (n_axes is not None and len(shape) != n_axes) or not shape or min(shape) < 1:
+        raise ValueError(f"shape must be {n_axes if n_axes is not None else 'a tuple of'} positive counts, got {shape}")
+    return shape
+
+
+def line(p0, p1, n):
+    """``n`` points from ``p0`` to ``p1``, both ends included (``n = 1``: ``p0``) -> float64 [n, d]"""
+    p0 = _vector(p0, "p0")
+    p1 = _vector(p1, "p1", p0.size)
+    (n,) = _shape(n, 1)
+    s = np.arange(n, dtype=np.float64) / max(n - 1, 1)
+    return p0 + s[:, None] * (p1 - p0)
+
+
+def plane(origin, e1, e2, shape):
+    """the points ``origin + (i + 1/2) / n1 * e1 + (j + 1/2) / n2 * e2`` of the parallelogram spanned by ``e1`` and ``e2`` at
+    ``origin``, ``shape = (n1, n2)`` -> float64 [n1 * n2, d], ``i`` the slow index (``result.reshape(n1, n2, d)``)"""
+    origin = _vector(origin, "origin")
+    e1, e2 = _vector(e1, "e1", origin.size), _vector(e2, "e2", origin.size)
+    n1, n2 = _shape(shape, 2)
+    s1, s2 = (np.arange(n1) + 0.5) / n1, (np.arange(n2) + 0.5) / n2
+    return (origin + s1[:, None, None] * e1 + s2[None, :, None] * e2).reshape(n1 * n2, origin.size)
+
+
+def raster(lo, hi, shape):
+    """pixel (voxel) centres of the uniform raster over the box ``[lo, hi]``: ``shape`` counts the pixels along x, y (, z) -- d
+    entries -- and the result is float64 [prod(shape), d] with the LAST axis running fastest: ``values.reshape(shape)`` is indexed
+    ``[ix, iy (, iz)]`` (``imshow`` wants its transpose)."""
+    lo = _vector(lo, "lo")
+    hi = _vector(hi, "hi", lo.size)
+    shape = _shape(shape, lo.size)
+    axes = [lo[a] + (np.arange(n) + 0.5) / n * (hi[a] - lo[a]) for a, n in enumerate(shape)]
+    return np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, lo.size)
+
+
+# ---- the probe ---------------------------------------------------------------------------------------------------------------
+class Probe:
+    """``points`` [Nq, d] located once in the grid (``centers`` [Nc, d], ``levels`` [Nc] or [Nc, 1], ``width``: the size of the
+    initial cell; numpy or torch, host or device).  ``nodes`` [Nn, d] and ``faces`` [Nc, 2^d] (the corner nodes of every cell) are
+    needed for ``mode="linear"`` only.  The grid is refused with ``ValueError`` when its cells are no disjoint dyadic boxes on one
+    lattice.
+
+    ``cell_ids`` (int32 [Nq], -1: no cell) and ``inside`` (bool [Nq]) come back in the caller's order, on the side (and as the kind
+    of array) the points came from.  ``sample`` takes fields [rows, (n_comp,) T] (``[rows]``: one snapshot; rows = cells for
+    ``mode="cell"``, nodes for ``mode="linear"``), float32 or float64, numpy or torch, host or device; a window ``field[:, t0:t1]``
+    of a scalar field that lives on the device is read where it lies.  Results are float64 [Nq, (n_comp,) T] on the side the field
+    came from, NaN where ``inside`` is False."""
+
+    def __init__(self, centers, levels, width, points, nodes=None, faces=None):
+        self._numpy = isinstance(points, np.ndarray)
+        points, centers, levels = _as_tensor(points, "points"), _as_tensor(centers, "centers"), _as_tensor(levels, "levels")
+        if centers.dim() != 2 or int(centers.shape[1]) not in (2, 3):
+            raise ValueError(f"expected centers [Nc, 2 | 3], got {tuple(centers.shape)}")
+        self.n_cells, self.dim = int(centers.shape[0]), int(centers.shape[1])
+        if points.dim() != 2 or int(points.shape[1]) != self.dim:
+            raise ValueError(f"expected points [Nq, {self.dim}], got {tuple(points.shape)}")
+        if levels.numel() != self.n_cells or levels.is_floating_point():
+            raise ValueError(f"expected one integer level per cell ({self.n_cells}), got {tuple(levels.shape)} {levels.dtype}")
+        if (nodes is None) != (faces is None):
+            raise ValueError("nodes and faces go together")
+        self.n_points = int(points.shape[0])
+        self._on_host = not points.is_cuda
+        self._index = hipops.cell_index(hipops.to_device(centers, pt.float64), hipops.to_device(levels.reshape(-1), pt.int32), width)
+        self._points = hipops.to_device(points, pt.float64)
+        self._faces, self.n_nodes = None, None
+        if faces is not None:
+            faces, nodes = _as_tensor(faces, "faces"), _as_tensor(nodes, "nodes")
+            if tuple(faces.shape) != (self.n_cells, 1 << self.dim) or faces.is_floating_point():
+                raise ValueError(f"expected integer faces [{self.n_cells}, {1 << self.dim}], got {tuple(faces.shape)} {faces.dtype}")
+            if nodes.dim() != 2 or int(nodes.shape[1]) != self.dim:
+                raise ValueError(f"expected nodes [Nn, {self.dim}], got {tuple(nodes.shape)}")
+            self.n_nodes = int(nodes.shape[0])
+            if int(faces.min()) < 0 or int(faces.max()) >= self.n_nodes:
+                raise ValueError(f"faces name nodes outside [0, {self.n_nodes})")
+            self._faces = hipops.to_device(faces, pt.int32)
+        if self.n_points:
+            # the points are launched in Hilbert order: neighbouring slots then read the same few field rows
+            self._rows = hipops.spatial_order(self._points)
+            self._ids = hipops.cell_locate(self._index, self._points, rows=self._rows)
+        else:
+            self._rows, self._ids = None, pt.empty(0, dtype=pt.int32, device=self._points.device)
+
+    @classmethod
+    def from_dataloader(cls, loader, points):
+        """the grid of an S^3 file (``data.Dataloader``): centres, levels, the size of the initial cell and, for ``mode="linear"``,
+        the corner nodes and faces"""
+        return cls(loader.vertices, loader.levels, loader._size_initial_cell, points, nodes=loader.nodes, faces=loader.faces)
+
+    @classmethod
+    def from_s_cube(cls, s_cube, points):
+        """the grid of a ``SparseSpatialSampling`` after ``execute_grid_generation``"""
+        if getattr(s_cube, "centers", None) is None:
+            raise ValueError("the grid has not been generated yet: call execute_grid_generation() first")
+        return cls(s_cube.centers, s_cube.levels, float(s_cube.size_initial_cell), points, nodes=s_cube.vertices, faces=s_cube.faces)
+
+    def _back(self, t):
+        if self._on_host:
+            hipops.synchronize()
+            t = t.cpu()
+        return t.numpy() if self._numpy and self._on_host else t
+
+    @property
+    def cell_ids(self):
+        return self._back(self._ids)
+
+    @property
+    def inside(self):
+        return self._back(self._ids >= 0)
+
+    def sample(self, field, mode="cell"):
+        """[rows, (n_comp,) T] -> float64 [Nq, (n_comp,) T]"""
+        if mode not in hipops.SAMPLE_MODES:
+            raise ValueError(f"unknown mode {mode!r}, expected one of {sorted(hipops.SAMPLE_MODES)}")
+        if mode == "linear" and self._faces is None:
+            raise ValueError("mode 'linear' blends the corner values of a cell: build the Probe with nodes and faces")
+        as_numpy = isinstance(field, np.ndarray)
+        field = _as_tensor(field, "field")
+        shape = tuple(int(v) for v in field.shape)
+        n_rows = self.n_cells if mode == "cell" else self.n_nodes
+        if not 1 <= len(shape) <= 3 or shape[0] != n_rows:
+            raise ValueError(f"{mode}: expected a field [{n_rows}, (n_comp,) T] on the grid's {'cells' if mode == 'cell' else 'nodes'}, got {shape}")
+        if 0 in shape:
+            raise ValueError(f"{mode}: empty field {shape}")
+        on_host = not field.is_cuda
+        dev_field = field if self._reads_in_place(field) else hipops.to_device(field if field.dtype in hipops.DTYPE_CODE else field.to(pt.float64))
+        if self.n_points:
+            res = hipops.cell_sample(self._ids, dev_field, mode, rows=self._rows, index=self._index, points=self._points, faces=self._faces)
+        else:
+            res = pt.empty((0,) + shape[1:], dtype=pt.float64, device=dev_field.device)
+        res = res.view((self.n_points,) + shape[1:])
+        if on_host:
+            hipops.synchronize()
+            res = res.cpu()
+        return res.numpy() if as_numpy else res
+
+    @staticmethod
+    def _reads_in_place(x):
+        """a contiguous device field, or a snapshot window ``field[:, t0:t1]`` of a resident 2-D one (the kernel has a row pitch)"""
+        if not (x.is_cuda and x.dtype in hipops.DTYPE_CODE and x.device == hipops.device()):
+            return False
+        return x.is_contiguous() or (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1])
