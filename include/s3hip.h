@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 14
+#define S3_ABI_VERSION 15
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -448,6 +448,44 @@ int s3_cell_sample(int mode, const int32_t *d_cell /*[nq]*/, int64_t nq, const i
                    const double *d_points /*[nq,dim]*/, const double *d_centers /*[n_cells,dim]*/, const int32_t *d_levels /*[n_cells]*/,
                    double width, const int32_t *d_faces /*[n_cells,2^dim]*/, int64_t n_cells, double *d_out, int64_t out_stride,
                    s3_stream stream);
+
+/* ---- isosurfaces (3-D) and contour lines (2-D) of node fields by marching simplices (csrc/iso.hip; no counterpart in the reference) ----
+ * Inputs: d_nodes [n_nodes][dim] f64; d_faces [n_cells][2^dim] int32 in the corner order above ((-,-), (-,+), (+,+), (+,-) in 2-D;
+ * that order at z+, then at z-, in 3-D); a field on the nodes, rows [row_len] f32 or f64 with pitch in_stride ELEMENTS (0 =
+ * row_len), read where they lie; a finite level.  Centres, levels and the width of the grid are not needed.
+ *   inside      node n at snapshot t iff (double) f[n][t] >= level: -0.0 is inside at level 0.0, a value equal to the level is inside
+ *   nothing     is emitted at t by a cell with a corner value that is NaN or +-inf at t, or with a corner id outside [0, n_nodes)
+ *               (nothing is loaded through such an id)
+ *   simplices   for each permutation pi of the axes, in lexicographic order of pi, the path p_0 = (-, .., -), p_{i+1} = p_i with
+ *               axis pi(i) switched to + (Kuhn): six tetrahedra around the diagonal from corner 4 to corner 2 of d_faces in 3-D, two
+ *               triangles around the diagonal from corner 0 to corner 2 in 2-D.  The decomposition is translation invariant and
+ *               matches across a face between two cells of one level; across a level jump the surface may crack at hanging nodes
+ *               (documented, not repaired).
+ *   primitives  of a simplex with path positions 0 .. dim, I the inside and O the outside positions, both ascending:
+ *                 3-D, one position s alone on its side (|I| = 1 | 3): one triangle over the edges (s,a), (s,b), (s,c), a < b < c
+ *                 3-D, I = {i,j}, O = {k,l}: the quad (i,k), (i,l), (j,l), (j,k) as the triangles (q0,q1,q2) and (q0,q2,q3)
+ *                 2-D: one segment over (s,a), (s,b)
+ *               per cell and snapshot sum over the simplices of min(|I|, dim + 1 - |I|): at most 12 in 3-D and 2 in 2-D
+ *   orientation the right-hand normal of a triangle points to the side f < level; in 2-D the side f >= level lies to the left of
+ *               q0 -> q1.  Where the natural order above gives the opposite, the last two vertices of the primitive are swapped
+ *               (both triangles of a quad together); that depends on the parity of pi and the inside mask only.
+ *   vertex      on a crossing edge, between the nodes a < b in GLOBAL node id whatever its direction in the simplex, in f64 as written:
+ *                 t = (level - f_a) / (f_b - f_a)        x = fma(t, x_b - x_a, x_a) per axis
+ *               t lies in [0, 1]; the same edge gives the same bits in every simplex and cell that shares it, so the output can be
+ *               welded by the key (a, b) without a tolerance.  Degenerate primitives (a vertex exactly on a node) are kept.
+ *   output      primitives ordered by (snapshot, cell in the caller's numbering, simplex, primitive within the simplex):
+ *               d_verts [n][dim][dim] f64, d_edges [n][dim][2] int32 (a < b), d_frac [n][dim] f64 (t), d_cells [n] int32
+ * s3_iso_count writes d_count[t][cell] (int32 [row_len][n_cells]); the caller scans it in place (s3_exclusive_scan, elem_bytes 4:
+ * positions never come from atomics) and reads back the total; s3_iso_emit takes the scan as d_offset and writes the primitives of
+ * (t, cell) at d_offset[t][cell] .. .  A (t, cell) whose offset equals its successor's does no further work; nothing is written at a
+ * position outside [0, capacity), whatever d_offset holds.  Both refuse a batch with 12 * n_cells * row_len >= 2^31 (2 * .. in 2-D).
+ * The bits depend on neither row_len, the load width, the element type (an f32 field gives the bits of its f64 copy) nor the run. */
+int s3_iso_count(const void *d_field, int dtype, int64_t row_len, int64_t in_stride, int64_t n_nodes, const int32_t *d_faces /*[n_cells,2^dim]*/,
+                 int64_t n_cells, int dim, double level, int32_t *d_count /*[row_len,n_cells]*/, s3_stream stream);
+int s3_iso_emit(const void *d_field, int dtype, int64_t row_len, int64_t in_stride, int64_t n_nodes, const int32_t *d_faces /*[n_cells,2^dim]*/,
+                int64_t n_cells, int dim, double level, const double *d_nodes /*[n_nodes,dim]*/, const int32_t *d_offset /*[row_len,n_cells]*/,
+                int64_t capacity, double *d_verts /*[capacity,dim,dim]*/, int32_t *d_edges /*[capacity,dim,2]*/, double *d_frac /*[capacity,dim]*/,
+                int32_t *d_cells /*[capacity]*/, s3_stream stream);
 
 /* ---- yardsticks of the measurement (bench.py's roofline line; no counterpart in the reference, not on any product path) ----
  * s3_yard_stream      a hand-written streaming kernel over d_src: every lane reads `reads` 16-byte vectors (coalesced) and

@@ -1,6 +1,6 @@
 // Rows of float32 or float64 read where they lie, VEC elements per load instruction: the vector type of (T, VEC), the loads, the host
 // rule that picks VEC for a launch and the step from (dtype, VEC) at run time to <T, VEC> at compile time.  Shared by every kernel
-// family that takes a `dtype` argument (metric.hip, export.hip, recon.hip, differential.hip, sample.hip, and through mfma_stage.h
+// family that takes a `dtype` argument (metric.hip, export.hip, recon.hip, differential.hip, sample.hip, iso.hip, and through mfma_stage.h
 // svd.hip and spectral.hip).  gfx950 only.
 //
 // VEC is chosen per LAUNCH, never per lane: every vector address of a launch is the base address plus multiples of a few byte
@@ -15,7 +15,8 @@
 //                                          in%8, out%16; else 1
 //   s3_recon_error (width follows the      4: row_len%4, grid%16; else 1                   2: row_len%2, grid%16; else 1
 //   grid; x orig f32 / f64)
-//   s3_grad_apply, s3_cell_sample          4: row_len%4, stride%4, base%16; else 1         2: row_len%2, stride%2, base%16; else 1
+//   s3_grad_apply, s3_cell_sample,         4: row_len%4, stride%4, base%16; else 1         2: row_len%2, stride%2, base%16; else 1
+//   s3_iso_count, s3_iso_emit
 //   s3_gram, s3_weighted_gram,             4 / 2 / 1 by base | stride*4 [| hop*4]          always 1
 //   s3_tall_gemm and the centred GEMMs,
 //   s3_segment_dft / s3_segment_psd
@@ -72,7 +73,7 @@ __device__ __forceinline__ void row_store(double *__restrict__ p, const double (
 // The widths a family instantiates per element type, as the OR of them (1 is always among them): a family declares this once.
 template <int F32, int F64> struct RowWidths { static constexpr int f32 = F32, f64 = F64; };
 using EveryRowWidth = RowWidths<4 | 2 | 1, 2 | 1>;      // s3_row_moments, s3_interp
-using WidestRowWidth = RowWidths<4 | 1, 2 | 1>;         // s3_recon_error, s3_grad_apply, s3_cell_sample: 16-byte loads or element loads
+using WidestRowWidth = RowWidths<4 | 1, 2 | 1>;         // s3_recon_error, s3_grad_apply, s3_cell_sample, s3_iso_*: 16-byte loads or element loads
 using StagedRowWidths = RowWidths<4 | 2 | 1, 1>;        // the f64 matrix-core kernels: float64 keeps the scalar form it always had
 using ScalarRows = RowWidths<1, 1>;                     // the element type alone
 

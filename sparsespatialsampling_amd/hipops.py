@@ -447,6 +447,108 @@ def cell_sample(ids, field, mode="cell", rows=None, out=None, index=None, points
     return out
 
 
+ISO_COUNT_BYTES = 256 << 20         # the largest count array [T_b, n_cells] int32 of one isosurface launch
+ISO_MAX_PRIMITIVES = {2: 2, 3: 12}  # per cell and snapshot
+
+
+def _iso_inputs(field, faces, level, who):
+    """-> (field as [n_nodes, T], T, in_stride, n_cells, dim, level)"""
+    if not (isinstance(field, pt.Tensor) and field.is_cuda and field.dtype in DTYPE_CODE and 1 <= field.dim() <= 2):
+        raise TypeError(f"{who}: float32 / float64 device field [n_nodes] or [n_nodes, T] required")
+    if field.dim() == 1:
+        field = field.contiguous().view(-1, 1)
+    t, in_stride = _pitched_rows(field, f"{who}(field)")
+    if t < 1 or int(field.shape[0]) < 1:
+        raise ValueError(f"{who}: empty field {tuple(field.shape)}")
+    if not (isinstance(faces, pt.Tensor) and faces.is_cuda and faces.dtype == pt.int32 and faces.is_contiguous() and faces.dim() == 2
+            and int(faces.shape[1]) in (4, 8)):
+        raise TypeError(f"{who}: faces must be a contiguous int32 device tensor [n_cells, 4 | 8]")
+    level = float(level)
+    if not np.isfinite(level):
+        raise ValueError(f"{who}: the level must be finite, got {level!r}")
+    return field, t, in_stride, int(faces.shape[0]), 2 if int(faces.shape[1]) == 4 else 3, level
+
+
+def _iso_out(out, shape, dtype, device, who, what):
+    numel = int(np.prod(shape))
+    if out is None:
+        return pt.empty(shape, dtype=dtype, device=device)
+    if not (isinstance(out, pt.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == dtype and out.numel() >= numel and out.device == device):
+        raise TypeError(f"{who}: {what} must be a contiguous {dtype} device tensor of at least {numel} values")
+    return out
+
+
+def iso_count(field, faces, level, out=None):
+    """primitives of the isosurface (3-D: triangles) or contour (2-D: segments) per snapshot and cell (s3_iso_count): ``field``
+    float32 / float64 [n_nodes] or [n_nodes, T] on the device (rows may be pitched: read where they lie), ``faces`` int32
+    [n_cells, 2^dim].  -> int32 [T, n_cells], written into ``out`` when given (a flat tensor with room to spare is taken)."""
+    field, t, in_stride, n_cells, dim, level = _iso_inputs(field, faces, level, "iso_count")
+    out = _iso_out(out, (t, n_cells), pt.int32, field.device, "iso_count", "out")
+    check(_lib.hip_lib().s3_iso_count(C.c_void_p(field.data_ptr()), DTYPE_CODE[field.dtype], t, in_stride,
+                                      int(field.shape[0]), _ptr(faces), n_cells, dim, level, _ptr(out), _stream()), "s3_iso_count")
+    return out
+
+
+def iso_emit(field, faces, level, nodes, offsets, capacity, verts=None, edges=None, frac=None, cells=None):
+    """the primitives themselves (s3_iso_emit): ``offsets`` int32 [T, n_cells] is the exclusive scan of what ``iso_count`` gave
+    for the same arguments, ``nodes`` float64 [n_nodes, dim], ``capacity`` the primitives the outputs have room for (nothing is
+    written past it).  -> (verts f64 [capacity, dim, dim], edges int32 [capacity, dim, 2], frac f64 [capacity, dim], cells int32
+    [capacity]), ordered by (snapshot, cell, simplex, primitive of the simplex)."""
+    field, t, in_stride, n_cells, dim, level = _iso_inputs(field, faces, level, "iso_emit")
+    n_nodes, capacity = int(field.shape[0]), int(capacity)
+    if not (isinstance(nodes, pt.Tensor) and nodes.is_cuda and nodes.dtype == pt.float64 and nodes.is_contiguous() and tuple(nodes.shape) == (n_nodes, dim)):
+        raise TypeError(f"iso_emit: nodes must be a contiguous float64 device tensor [{n_nodes}, {dim}]")
+    if not (isinstance(offsets, pt.Tensor) and offsets.is_cuda and offsets.dtype == pt.int32 and offsets.is_contiguous() and offsets.numel() >= t * n_cells):
+        raise TypeError(f"iso_emit: offsets must be a contiguous int32 device tensor of {t} x {n_cells} entries")
+    if capacity < 0:
+        raise ValueError(f"iso_emit: capacity {capacity}")
+    dev = field.device
+    verts = _iso_out(verts, (capacity, dim, dim), pt.float64, dev, "iso_emit", "verts")
+    edges = _iso_out(edges, (capacity, dim, 2), pt.int32, dev, "iso_emit", "edges")
+    frac = _iso_out(frac, (capacity, dim), pt.float64, dev, "iso_emit", "frac")
+    cells = _iso_out(cells, (capacity,), pt.int32, dev, "iso_emit", "cells")
+    check(_lib.hip_lib().s3_iso_emit(C.c_void_p(field.data_ptr()), DTYPE_CODE[field.dtype], t, in_stride, n_nodes, _ptr(faces), n_cells, dim, level,
+                                     _ptr(nodes), _ptr(offsets), capacity, _ptr(verts), _ptr(edges), _ptr(frac), _ptr(cells), _stream()), "s3_iso_emit")
+    return verts, edges, frac, cells
+
+
+def iso_batch_columns(n_cells, dim, count_bytes=ISO_COUNT_BYTES):
+    """the snapshots one launch may take: the count array [T_b, n_cells] int32 stays under ``count_bytes`` and
+    max primitives * n_cells * T_b under 2^31, so that the int32 offsets cannot overflow"""
+    n_cells = max(int(n_cells), 1)
+    return max(1, min(int(count_bytes) // (4 * n_cells), ((1 << 31) - 1) // (ISO_MAX_PRIMITIVES[dim] * n_cells)))
+
+
+def iso_extract(field, faces, nodes, level, count_only=False, count_bytes=ISO_COUNT_BYTES):
+    """count, scan (s3_exclusive_scan, in place), read back the totals, emit -- in batches of ``iso_batch_columns`` snapshots.
+    -> (offsets int64 numpy [T + 1], verts, edges, frac, cells) as ``iso_emit`` gives them, with exactly offsets[-1] primitives;
+    ``count_only``: (offsets,) after the first pass and the scan alone."""
+    field, t, _, n_cells, dim, level = _iso_inputs(field, faces, level, "iso_extract")
+    lib, dev = _lib.hip_lib(), field.device
+    offsets, parts = [np.zeros(1, dtype=np.int64)], []
+    step = iso_batch_columns(n_cells, dim, count_bytes)
+    for c0 in range(0, t, step):
+        window = field[:, c0:c0 + step]
+        t_b = int(window.shape[1])
+        n = t_b * n_cells
+        scan = pt.empty(n + 1, dtype=pt.int32, device=dev)                      # one entry more: its scan is the total
+        scan[n:].zero_()
+        if n_cells:
+            iso_count(window, faces, level, out=scan)
+        else:
+            scan.zero_()
+        check(lib.s3_exclusive_scan(_ptr(scan), _ptr(scan), n + 1, 4, _stream()), "s3_exclusive_scan")
+        starts = scan[::max(n_cells, 1)][:t_b + 1] if n_cells else scan.new_zeros(t_b + 1)
+        starts = starts.cpu().numpy().astype(np.int64)                          # (waits for the stream)
+        offsets.append(offsets[-1][-1] + starts[1:])
+        if not count_only:
+            parts.append(iso_emit(window, faces, level, nodes, scan, int(starts[-1])))
+    offsets = np.concatenate(offsets)
+    if count_only:
+        return (offsets,)
+    return (offsets,) + tuple(p[0] if len(parts) == 1 else pt.cat(p) for p in zip(*parts))
+
+
 def _pitched_matrix(t, who):
     """row pitch in elements of a 2-D f32 / f64 device matrix with unit inner stride, read where it lies"""
     if not (t.is_cuda and t.dtype in DTYPE_CODE and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
