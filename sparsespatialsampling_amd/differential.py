@@ -26,16 +26,15 @@ import numpy as np
 import torch as pt
 
 from . import hipops
+from .arrays import Side, as_tensor, default_neighbors, hilbert_knn, resident
 
 
 def _default(dim, n_points, n_neighbors):
     """the stencil size: 8 | 26 by default, capped at the other points of the cloud and at what one search returns"""
-    k = (8 if dim == 2 else 26) if n_neighbors is None else int(n_neighbors)
-    if k < 1:
-        raise ValueError(f"n_neighbors must be positive, got {k}")
+    k = default_neighbors(dim, n_neighbors, min(n_points - 1, hipops.GRAD_MAX_K))
     if n_points < dim + 1:
         raise ValueError(f"a gradient in {dim}-D needs at least {dim + 1} points, got {n_points}")
-    return min(k, n_points - 1, hipops.GRAD_MAX_K)
+    return k
 
 
 def _check_points(points):
@@ -49,20 +48,13 @@ def _check_power(power):
     return int(power)
 
 
-def _as_tensor(x, what):
-    if isinstance(x, np.ndarray):
-        return pt.from_numpy(np.ascontiguousarray(x))
-    if not isinstance(x, pt.Tensor):
-        raise TypeError(f"{what} must be a numpy array or a torch tensor, got {type(x).__name__}")
-    return x
-
-
-def drop_self(idx):
+def drop_self(idx, rows=None):
     """``idx`` int32 [N, k + 1] on the device, the k + 1 nearest points of the cloud to each of its points in ``KnnIndex.query`` order
     -> [N, k]: the entry that is the point itself removed, or the last one where more than k coincident copies crowd it out.  Not
-    column 0: among duplicates the point itself may be listed later."""
+    column 0: among duplicates the point itself may be listed later.  ``rows`` int32 [N]: the point each row of ``idx`` belongs to
+    (None: row j is point j)."""
     n = int(idx.shape[0])
-    hit = idx == pt.arange(n, dtype=pt.int32, device=idx.device).unsqueeze(1)
+    hit = idx == (pt.arange(n, dtype=pt.int32, device=idx.device) if rows is None else rows).unsqueeze(1)
     hit[:, -1] |= ~hit.any(dim=1)
     return idx[~hit].view(n, int(idx.shape[1]) - 1).contiguous()
 
@@ -76,29 +68,20 @@ class Gradient:
     points came from).
 
     Fields are [N, (n_comp,) T] (``[N]``: one snapshot), float32 or float64, numpy or torch, host or device; a window
-    ``field[:, t0:t1]`` of a scalar field that lives on the device is read where it lies.  Results are float64 and come back on
-    the side (and as the kind of array) the field came from; ``out`` may name the array to fill."""
+    ``field[:, t0:t1]`` of a scalar field that lives on the device is read where it lies (``arrays.resident``).  Results are
+    float64 and come back on the side (and as the kind of array) the field came from; ``out`` may name the array to fill."""
 
     def __init__(self, points, n_neighbors=None, power=2):
-        self._numpy = isinstance(points, np.ndarray)
-        points = _as_tensor(points, "points")
+        points, self._side = as_tensor(points, "points"), Side(points)
         _check_points(points)
         power = _check_power(power)
         self.n_points, self.dim = int(points.shape[0]), int(points.shape[1])
         self.n_neighbors = _default(self.dim, self.n_points, n_neighbors)
         self.power = power
-        self._on_host = not points.is_cuda
         pts = hipops.to_device(points, pt.float64)
-        knn = hipops.KnnIndex(pts)
-        try:
-            idx, _ = knn.query(pts, self.n_neighbors + 1)
-            idx = drop_self(idx)
-            hipops.synchronize()
-        finally:
-            knn.close()
         # the points are launched in Hilbert order: neighbouring slots then gather the same few field rows
-        self._rows = hipops.spatial_order(pts)
-        self._idx = hipops.gather_rows(idx, self._rows, pt.empty_like(idx))
+        idx, _, self._rows = hilbert_knn(pts, pts, self.n_neighbors + 1)
+        self._idx = drop_self(idx, self._rows)
         self._coef, flag, self.n_degenerate = hipops.grad_coeff(pts, self._idx, power, rows=self._rows)
         degenerate = pt.zeros(self.n_points, dtype=pt.bool, device=pts.device)
         degenerate[self._rows.long()] = flag.bool()
@@ -114,10 +97,7 @@ class Gradient:
 
     @property
     def degenerate(self):
-        d = self._degenerate
-        if self._on_host:
-            d = d.cpu()
-        return d.numpy() if self._numpy and self._on_host else d
+        return self._side.back(self._degenerate)
 
     # ---- the six quantities ---------------------------------------------------------------------------------------------
     def gradient(self, field, out=None):
@@ -159,8 +139,8 @@ class Gradient:
         return (n,) + tail
 
     def _apply(self, mode, field, out):
-        as_numpy = isinstance(field, np.ndarray)
-        field = _as_tensor(field, "field")
+        field, side = as_tensor(field, "field"), Side(field)
+        as_numpy = side.numpy
         shape = tuple(int(v) for v in field.shape)
         vector = mode not in ("gradient", "magnitude")
         if vector:
@@ -171,7 +151,6 @@ class Gradient:
         if 0 in shape:
             raise ValueError(f"{mode}: empty field {shape}")
         want = self._out_shape(mode, shape)
-        on_host = not field.is_cuda
         if out is not None:
             if not isinstance(out, np.ndarray if as_numpy else pt.Tensor):
                 raise TypeError(f"{mode}: out must be the kind of array the field is ({'numpy.ndarray' if as_numpy else 'torch.Tensor'}), "
@@ -181,23 +160,13 @@ class Gradient:
                 raise TypeError(f"{mode}: out must be float64 on the side of the field, got {o.dtype} on {o.device}")
             if tuple(o.shape) != want:
                 raise ValueError(f"{mode}: out has shape {tuple(o.shape)}, the result {want}")
-        dev_field = field if self._reads_in_place(field) else hipops.to_device(field if field.dtype in hipops.DTYPE_CODE else field.to(pt.float64))
-        direct = out is not None and not on_host and out.is_contiguous() and out.device == dev_field.device
+        dev_field = resident(field)
+        direct = out is not None and not side.host and out.is_contiguous() and out.device == dev_field.device
         res = hipops.grad_apply(self._coef, self._idx, dev_field, mode, rows=self._rows, out=out if direct else None)
         if direct:
             return out
-        res = res.view(want)
-        if on_host:
-            hipops.synchronize()
-            res = res.cpu()
-        if out is not None:
-            (pt.from_numpy(out) if as_numpy else out).copy_(res)
-            return out
-        return res.numpy() if as_numpy else res
-
-    @staticmethod
-    def _reads_in_place(x):
-        """a contiguous device field, or a snapshot window ``field[:, t0:t1]`` of a resident 2-D one (the kernel has a row pitch)"""
-        if not (x.is_cuda and x.dtype in hipops.DTYPE_CODE and x.device == hipops.device()):
-            return False
-        return x.is_contiguous() or (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1])
+        res = side.back(res.view(want))
+        if out is None:
+            return res
+        o.copy_(pt.as_tensor(res))
+        return out

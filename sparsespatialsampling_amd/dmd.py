@@ -32,6 +32,7 @@ import numpy as np
 import torch as pt
 
 from . import hipops
+from .arrays import Side, resident_matrix
 from .svd import _eigh, optimal_rank
 
 log = logging.getLogger(__name__)
@@ -148,14 +149,9 @@ class DMD:
     def __init__(self, data_matrix, dt, rank=None, optimal=False, cell_area=None):
         n_cells, n_comp, t = _check_arguments(data_matrix, dt, rank, cell_area)
         self.dt, self.optimal = float(dt), bool(optimal)
-        self._on_host = not data_matrix.is_cuda
+        self._side = Side(data_matrix)
         self._shape = tuple(data_matrix.shape)
-        dev = hipops.device()
-        if data_matrix.is_cuda and data_matrix.device == dev:
-            d = data_matrix                                                   # read where it lies, pitch included
-        else:
-            d = hipops.to_device(data_matrix)                                 # an upload in the matrix's own dtype
-        d2 = d.reshape(n_cells * n_comp, t) if n_comp is not None else d
+        d2 = resident_matrix(data_matrix, n_cells, n_comp, t)               # read where it lies, or uploaded in its own dtype
         weight = None
         if cell_area is not None:
             weight = hipops.to_device(cell_area, pt.float64).reshape(-1)
@@ -179,7 +175,7 @@ class DMD:
             log.warning(f"DMD: rank {r} reaches below {RANK_RANGE:g} of the largest singular value, where the Gram matrix resolves "
                         f"nothing; {usable} modes are kept.")
             r = usable
-        self.svd = SimpleNamespace(s=self._out(s_all[:r].clone()), V=self._out(vec[:, :r].contiguous()), rank=r, opt_rank=opt_rank)
+        self.svd = SimpleNamespace(s=self._side.back(s_all[:r].clone()), V=self._side.back(vec[:, :r].contiguous()), rank=r, opt_rank=opt_rank)
         small = _small_problem(gram, s_all[:r], vec[:, :r], self.dt, self.optimal)
         self._gram, self._small = gram, small
         lam_c, b = small["eigvals"], small["amplitude"]
@@ -195,37 +191,34 @@ class DMD:
         hipops.synchronize()                                                  # (the caller's matrix is not kept alive)
 
     # ---- small members ----
-    def _out(self, x):
-        return x if self._on_host else x.to(hipops.device())
-
     @property
     def eigvals(self):
-        return self._out(self._small["eigvals"])
+        return self._side.back(self._small["eigvals"])
 
     @property
     def eigvecs(self):
-        return self._out(self._small["eigvecs"])
+        return self._side.back(self._small["eigvecs"])
 
     @property
     def amplitude(self):
-        return self._out(self._small["amplitude"])
+        return self._side.back(self._small["amplitude"])
 
     @property
     def frequency(self):
-        return self._out(self._frequency)
+        return self._side.back(self._frequency)
 
     @property
     def growth_rate(self):
-        return self._out(self._growth)
+        return self._side.back(self._growth)
 
     @property
     def dynamics(self):
-        return self._out(self._dynamics)
+        return self._side.back(self._dynamics)
 
     @property
     def integral_contribution(self):
         """``||phi_j||_a * sum_t |b_j lambda_j^t|`` (the weighted mode norm from diag(B^H G_YY B))"""
-        return self._out(self._mode_norm * self._dynamics.abs().sum(1))
+        return self._side.back(self._mode_norm * self._dynamics.abs().sum(1))
 
     @property
     def modes(self):
@@ -233,7 +226,7 @@ class DMD:
         r = self.svd.rank
         z = pt.view_as_complex(self._modes2.reshape(-1, r, 2))
         z = z.reshape(self._shape[:-1] + (r,))
-        return z.cpu() if self._on_host else z
+        return self._side.back(z)
 
     def top_modes(self, n=None, integral=False, f_min=-math.inf, f_max=math.inf):
         """indices of the modes with ``f_min <= frequency < f_max``, ordered by descending |b_j| or (``integral``) by descending
@@ -245,7 +238,7 @@ class DMD:
             if int(n) < 0:
                 raise ValueError(f"n must not be negative, got {n}")
             order = order[:int(n)]
-        return self._out(order)
+        return self._side.back(order)
 
     # ---- N-sized members ----
     def _window(self, t0, t1):
@@ -261,7 +254,7 @@ class DMD:
         rhs = _interleave(dynamics.conj().T).T.contiguous()                   # [2r, n_t]
         out = hipops.tall_gemm(self._modes2, hipops.to_device(rhs))
         out = out.reshape(self._shape[:-1] + (dynamics.shape[1],))
-        return pt.from_numpy(hipops.to_host(out)) if self._on_host else out
+        return self._side.back(out)
 
     def reconstruction(self, t0=0, t1=None):
         """``Re(Phi diag(b) Vand[:, t0:t1])``: real float64 [N_cells, (N_dims,) t1 - t0].  Nothing of size N x T exists unless all
@@ -286,4 +279,4 @@ class DMD:
         the squared residual norm is the difference of terms of the size of G_tt and good to about 64 T eps G_tt only, so a
         relative error below about 1e-6 is not resolved (a materialised residual is, when it matters)."""
         err, _ = _error_from_gram(self._gram, _coefficients(self._small["b_matrix"], self._dynamics))
-        return self._out(err)
+        return self._side.back(err)

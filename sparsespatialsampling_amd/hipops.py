@@ -40,6 +40,64 @@ def _host_f64(values, n=3):
     return a
 
 
+def _row_layout(t):
+    """(row_len, stride in elements) of a tensor whose leading axis is the row axis when its rows can be read where they lie:
+    contiguous [n, ...], or a 2-D view with unit inner stride and a pitch >= the row length (``buf[:, a:b]``); None otherwise.
+    Shape and strides alone: no device access."""
+    if t.dim() < 1:
+        return None
+    row_len = int(np.prod(t.shape[1:])) if t.dim() > 1 else 1
+    if t.is_contiguous():
+        return row_len, row_len
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= row_len:
+        return row_len, int(t.stride(0))
+    return None
+
+
+def _field_rows(field, who, max_dim=3):
+    """(n_comp, T, in_stride) of a field [n] (one snapshot), [n, T] (rows may be pitched: read where they lie) or, with
+    ``max_dim`` 3, [n, n_comp, T] contiguous.  Shape and strides alone; the caller answers for device and dtype."""
+    if field.dim() == 3 and max_dim == 3:
+        if not field.is_contiguous():
+            raise TypeError(f"{who}: a field [n, n_comp, T] must be contiguous")
+        n_comp, t = int(field.shape[1]), int(field.shape[2])
+        return n_comp, t, n_comp * t
+    layout = _row_layout(field) if field.dim() <= 2 else None
+    if layout is None:
+        raise TypeError(f"{who}: rows must be contiguous (a row pitch is allowed for a 2-D tensor)")
+    return (1,) + layout
+
+
+def _launch_rows(rows, n, who):
+    """the launch order ``rows`` (None: slot i is row i): int32 [n] on the device, contiguous as the kernels index it"""
+    if rows is not None and not (isinstance(rows, pt.Tensor) and rows.is_cuda and rows.dtype == pt.int32 and rows.numel() == n
+                                 and rows.is_contiguous()):
+        raise TypeError(f"{who}: rows must be a contiguous int32 device tensor [{n}]")
+    return rows
+
+
+def _out_tensor(out, shape, dtype, device, who, what="out", at_least=False):
+    """``out`` when it can take ``shape`` values of ``dtype`` on ``device`` (``at_least``: or more), a new tensor for None"""
+    if out is None:
+        return pt.empty(shape, dtype=dtype, device=device)
+    numel = int(np.prod(shape))
+    if not (isinstance(out, pt.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == dtype and out.device == device
+            and (out.numel() >= numel if at_least else out.numel() == numel)):
+        raise TypeError(f"{who}: {what} must be a contiguous {dtype} device tensor of {'at least ' if at_least else ''}"
+                        f"{' x '.join(str(int(v)) for v in shape)} values")
+    return out
+
+
+def _component_groups(n_comp):
+    """(first component, components) of the launches of a field: the kernels take up to three components at a time"""
+    return ((c0, min(3, n_comp - c0)) for c0 in range(0, n_comp, 3))
+
+
+def _scratch(nbytes, device):
+    """``nbytes`` of device scratch memory, 8-byte aligned"""
+    return pt.empty((int(nbytes) + 7) // 8, dtype=pt.float64, device=device)
+
+
 def device():
     """The torch device of the hot path; raises HipUnavailableError when there is none (no CPU fallback)."""
     _lib.require_device()
@@ -195,12 +253,10 @@ def _pitched_rows(t, who):
     slice ``buf[:, :L]`` of a wider buffer"""
     if not t.is_cuda or t.dtype not in DTYPE_CODE or t.dim() < 1:
         raise TypeError(f"{who}: float32 / float64 device tensor [n, ...] required")
-    row_len = int(np.prod(t.shape[1:])) if t.dim() > 1 else 1
-    if t.is_contiguous():
-        return row_len, row_len
-    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= row_len:
-        return row_len, int(t.stride(0))
-    raise TypeError(f"{who}: rows must be contiguous (a row pitch is allowed for a 2-D tensor)")
+    layout = _row_layout(t)
+    if layout is None:
+        raise TypeError(f"{who}: rows must be contiguous (a row pitch is allowed for a 2-D tensor)")
+    return layout
 
 
 def recon_error(w, idx, grid, orig, rows=None, scale=None, mean=None, m2=None):
@@ -219,20 +275,17 @@ def recon_error(w, idx, grid, orig, rows=None, scale=None, mean=None, m2=None):
     if g_stride != row_len or o_len != row_len or row_len < 1:
         raise TypeError("recon_error: grid must be contiguous and grid / orig rows of one length >= 1")
     nc, n_orig = int(grid.shape[0]), int(orig.shape[0])
-    if rows is not None and not (rows.dtype == pt.int32 and rows.numel() == n):
-        raise TypeError("recon_error: rows must be int32 [n]")
+    _launch_rows(rows, n, "recon_error")
     if (rows is None and n_orig != n) or n_orig < n or nc < 1:
         raise TypeError("recon_error: one original row per point required (or a row list)")
     if scale is not None and not (scale.dtype == pt.float64 and scale.numel() == n):
         raise TypeError("recon_error: scale must be float64 [n]")
     dev = w.device
-    mean = pt.empty(n_orig, dtype=pt.float64, device=dev) if mean is None else mean
-    m2 = pt.empty(n_orig, dtype=pt.float64, device=dev) if m2 is None else m2
-    if not (mean.dtype == pt.float64 and m2.dtype == pt.float64 and mean.numel() == n_orig and m2.numel() == n_orig):
-        raise TypeError("recon_error: mean / m2 must be float64 [n_orig]")
+    mean = _out_tensor(mean, (n_orig,), pt.float64, dev, "recon_error", "mean")
+    m2 = _out_tensor(m2, (n_orig,), pt.float64, dev, "recon_error", "m2")
     colsum = pt.empty((2, row_len), dtype=pt.float64, device=dev)
     lib = _lib.hip_lib()
-    scratch = pt.empty((lib.s3_recon_error_scratch_bytes(n, row_len) + 7) // 8, dtype=pt.float64, device=dev)
+    scratch = _scratch(lib.s3_recon_error_scratch_bytes(n, row_len), dev)
     check(lib.s3_recon_error(_ptr(w), _ptr(idx), n, k, _ptr(grid), DTYPE_CODE[grid.dtype], nc, C.c_void_p(orig.data_ptr()),
                              DTYPE_CODE[orig.dtype], n_orig, o_stride, row_len, _ptr(rows), _ptr(scale), _ptr(mean), _ptr(m2),
                              _ptr(colsum), _ptr(scratch), _stream()), "s3_recon_error")
@@ -258,8 +311,7 @@ def grad_coeff(points, idx, power=2, rows=None):
     n, dim = int(points.shape[0]), int(points.shape[1])
     if not (idx.is_cuda and idx.dtype == pt.int32 and idx.dim() == 2 and int(idx.shape[0]) == n):
         raise TypeError(f"grad_coeff: idx must be an int32 device tensor [{n}, k]")
-    if rows is not None and not (rows.is_cuda and rows.dtype == pt.int32 and rows.numel() == n):
-        raise TypeError(f"grad_coeff: rows must be an int32 device tensor [{n}]")
+    _launch_rows(rows, n, "grad_coeff")
     k = int(idx.shape[1])
     coef = pt.empty((n, k, dim), dtype=pt.float64, device=points.device)
     flag = pt.empty(n, dtype=pt.uint8, device=points.device)
@@ -285,31 +337,18 @@ def grad_apply(coef, idx, field, mode, rows=None, out=None):
         raise TypeError("grad_apply: float32 / float64 device field [n], [n, T] or [n, n_comp, T] required")
     if int(field.shape[0]) != n:
         raise ValueError(f"grad_apply: the field has {int(field.shape[0])} rows, the stencils {n}")
-    if field.dim() == 3:
-        n_comp, t = int(field.shape[1]), int(field.shape[2])
-        if not field.is_contiguous():
-            raise TypeError("grad_apply: a field [n, n_comp, T] must be contiguous")
-        in_stride = n_comp * t
-    else:
-        n_comp = 1
-        t, in_stride = _pitched_rows(field, "grad_apply(field)")
+    n_comp, t, in_stride = _field_rows(field, "grad_apply")
     if t < 1 or n_comp < 1:
         raise ValueError(f"grad_apply: empty field {tuple(field.shape)}")
     vector_mode = mode not in ("gradient", "magnitude")
     if vector_mode and n_comp != dim:
         raise ValueError(f"grad_apply: {mode} needs a vector field [n, {dim}, T], got {tuple(field.shape)}")
-    if rows is not None and not (rows.is_cuda and rows.dtype == pt.int32 and rows.numel() == n):
-        raise TypeError(f"grad_apply: rows must be an int32 device tensor [{n}]")
+    _launch_rows(rows, n, "grad_apply")
     n_out = grad_n_out(mode, dim, n_comp)
-    if out is None:
-        out = pt.empty((n, n_out, t), dtype=pt.float64, device=field.device)
-    elif not (isinstance(out, pt.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == pt.float64
-              and out.numel() == n * n_out * t and out.device == field.device):
-        raise TypeError(f"grad_apply: out must be a contiguous float64 device tensor of {n} x {n_out} x {t} values")
+    out = _out_tensor(out, (n, n_out, t), pt.float64, field.device, "grad_apply")
     lib, item = _lib.hip_lib(), field.element_size()
     per_comp = dim if mode == "gradient" else 1
-    for c0 in range(0, n_comp, 3) if n_comp > 3 else (0,):
-        group = min(3, n_comp - c0)
+    for c0, group in _component_groups(n_comp):
         check(lib.s3_grad_apply(_ptr(coef), _ptr(idx), n, k, dim, C.c_void_p(field.data_ptr() + c0 * t * item), DTYPE_CODE[field.dtype],
                                 group, t, in_stride, _ptr(rows), GRAD_MODES[mode], C.c_void_p(out.data_ptr() + c0 * per_comp * t * 8),
                                 n_out * t, _stream()), "s3_grad_apply")
@@ -377,12 +416,8 @@ def cell_locate(index, points, rows=None, out=None):
     if not isinstance(index, CellIndex):
         raise TypeError("cell_locate: index must be what cell_index returned")
     nq = _query_points(points, index.dim, "cell_locate")
-    if rows is not None and not (rows.is_cuda and rows.dtype == pt.int32 and rows.numel() == nq and rows.is_contiguous()):
-        raise TypeError(f"cell_locate: rows must be a contiguous int32 device tensor [{nq}]")
-    if out is None:
-        out = pt.empty(nq, dtype=pt.int32, device=points.device)
-    elif not (out.is_cuda and out.dtype == pt.int32 and out.numel() == nq and out.is_contiguous()):
-        raise TypeError(f"cell_locate: out must be a contiguous int32 device tensor [{nq}]")
+    _launch_rows(rows, nq, "cell_locate")
+    out = _out_tensor(out, (nq,), pt.int32, points.device, "cell_locate")
     check(_lib.hip_lib().s3_cell_locate(_ptr(index.starts), _ptr(index.ends), _ptr(index.ids), index.n_cells, index.dim, index.depth,
                                         C.c_void_p(index.origin.ctypes.data), index.h_min, _ptr(points), nq, _ptr(rows), _ptr(out),
                                         _stream()), "s3_cell_locate")
@@ -406,19 +441,11 @@ def cell_sample(ids, field, mode="cell", rows=None, out=None, index=None, points
     nq = int(ids.numel())
     if not (isinstance(field, pt.Tensor) and field.is_cuda and field.dtype in DTYPE_CODE and 1 <= field.dim() <= 3):
         raise TypeError("cell_sample: float32 / float64 device field [rows], [rows, T] or [rows, n_comp, T] required")
-    if field.dim() == 3:
-        n_comp, t = int(field.shape[1]), int(field.shape[2])
-        if not field.is_contiguous():
-            raise TypeError("cell_sample: a field [rows, n_comp, T] must be contiguous")
-        in_stride = n_comp * t
-    else:
-        n_comp = 1
-        t, in_stride = _pitched_rows(field, "cell_sample(field)")
+    n_comp, t, in_stride = _field_rows(field, "cell_sample")
     n_rows = int(field.shape[0])
     if t < 1 or n_comp < 1 or n_rows < 1:
         raise ValueError(f"cell_sample: empty field {tuple(field.shape)}")
-    if rows is not None and not (rows.is_cuda and rows.dtype == pt.int32 and rows.numel() == nq and rows.is_contiguous()):
-        raise TypeError(f"cell_sample: rows must be a contiguous int32 device tensor [{nq}]")
+    _launch_rows(rows, nq, "cell_sample")
     dim, n_cells, width, centers, levels = 0, 0, 0.0, None, None
     if mode == "linear":
         if index is None or points is None or faces is None:
@@ -433,14 +460,9 @@ def cell_sample(ids, field, mode="cell", rows=None, out=None, index=None, points
             raise TypeError(f"cell_sample: faces must be a contiguous int32 device tensor [{n_cells}, {1 << dim}]")
     else:
         points = faces = None
-    if out is None:
-        out = pt.empty((nq, n_comp, t), dtype=pt.float64, device=field.device)
-    elif not (isinstance(out, pt.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == pt.float64
-              and out.numel() == nq * n_comp * t and out.device == field.device):
-        raise TypeError(f"cell_sample: out must be a contiguous float64 device tensor of {nq} x {n_comp} x {t} values")
+    out = _out_tensor(out, (nq, n_comp, t), pt.float64, field.device, "cell_sample")
     lib, item = _lib.hip_lib(), field.element_size()
-    for c0 in range(0, n_comp, 3):
-        group = min(3, n_comp - c0)
+    for c0, group in _component_groups(n_comp):
         check(lib.s3_cell_sample(SAMPLE_MODES[mode], _ptr(ids), nq, _ptr(rows), C.c_void_p(field.data_ptr() + c0 * t * item),
                                  DTYPE_CODE[field.dtype], group, t, in_stride, n_rows, dim, _ptr(points), _ptr(centers), _ptr(levels), width,
                                  _ptr(faces), n_cells, C.c_void_p(out.data_ptr() + c0 * t * 8), n_comp * t, _stream()), "s3_cell_sample")
@@ -457,7 +479,7 @@ def _iso_inputs(field, faces, level, who):
         raise TypeError(f"{who}: float32 / float64 device field [n_nodes] or [n_nodes, T] required")
     if field.dim() == 1:
         field = field.contiguous().view(-1, 1)
-    t, in_stride = _pitched_rows(field, f"{who}(field)")
+    _, t, in_stride = _field_rows(field, who, 2)
     if t < 1 or int(field.shape[0]) < 1:
         raise ValueError(f"{who}: empty field {tuple(field.shape)}")
     if not (isinstance(faces, pt.Tensor) and faces.is_cuda and faces.dtype == pt.int32 and faces.is_contiguous() and faces.dim() == 2
@@ -469,21 +491,12 @@ def _iso_inputs(field, faces, level, who):
     return field, t, in_stride, int(faces.shape[0]), 2 if int(faces.shape[1]) == 4 else 3, level
 
 
-def _iso_out(out, shape, dtype, device, who, what):
-    numel = int(np.prod(shape))
-    if out is None:
-        return pt.empty(shape, dtype=dtype, device=device)
-    if not (isinstance(out, pt.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == dtype and out.numel() >= numel and out.device == device):
-        raise TypeError(f"{who}: {what} must be a contiguous {dtype} device tensor of at least {numel} values")
-    return out
-
-
 def iso_count(field, faces, level, out=None):
     """primitives of the isosurface (3-D: triangles) or contour (2-D: segments) per snapshot and cell (s3_iso_count): ``field``
     float32 / float64 [n_nodes] or [n_nodes, T] on the device (rows may be pitched: read where they lie), ``faces`` int32
     [n_cells, 2^dim].  -> int32 [T, n_cells], written into ``out`` when given (a flat tensor with room to spare is taken)."""
     field, t, in_stride, n_cells, dim, level = _iso_inputs(field, faces, level, "iso_count")
-    out = _iso_out(out, (t, n_cells), pt.int32, field.device, "iso_count", "out")
+    out = _out_tensor(out, (t, n_cells), pt.int32, field.device, "iso_count", at_least=True)
     check(_lib.hip_lib().s3_iso_count(C.c_void_p(field.data_ptr()), DTYPE_CODE[field.dtype], t, in_stride,
                                       int(field.shape[0]), _ptr(faces), n_cells, dim, level, _ptr(out), _stream()), "s3_iso_count")
     return out
@@ -503,10 +516,10 @@ def iso_emit(field, faces, level, nodes, offsets, capacity, verts=None, edges=No
     if capacity < 0:
         raise ValueError(f"iso_emit: capacity {capacity}")
     dev = field.device
-    verts = _iso_out(verts, (capacity, dim, dim), pt.float64, dev, "iso_emit", "verts")
-    edges = _iso_out(edges, (capacity, dim, 2), pt.int32, dev, "iso_emit", "edges")
-    frac = _iso_out(frac, (capacity, dim), pt.float64, dev, "iso_emit", "frac")
-    cells = _iso_out(cells, (capacity,), pt.int32, dev, "iso_emit", "cells")
+    verts = _out_tensor(verts, (capacity, dim, dim), pt.float64, dev, "iso_emit", "verts", at_least=True)
+    edges = _out_tensor(edges, (capacity, dim, 2), pt.int32, dev, "iso_emit", "edges", at_least=True)
+    frac = _out_tensor(frac, (capacity, dim), pt.float64, dev, "iso_emit", "frac", at_least=True)
+    cells = _out_tensor(cells, (capacity,), pt.int32, dev, "iso_emit", "cells", at_least=True)
     check(_lib.hip_lib().s3_iso_emit(C.c_void_p(field.data_ptr()), DTYPE_CODE[field.dtype], t, in_stride, n_nodes, _ptr(faces), n_cells, dim, level,
                                      _ptr(nodes), _ptr(offsets), capacity, _ptr(verts), _ptr(edges), _ptr(frac), _ptr(cells), _stream()), "s3_iso_emit")
     return verts, edges, frac, cells
@@ -551,9 +564,15 @@ def iso_extract(field, faces, nodes, level, count_only=False, count_bytes=ISO_CO
 
 def _pitched_matrix(t, who):
     """row pitch in elements of a 2-D f32 / f64 device matrix with unit inner stride, read where it lies"""
-    if not (t.is_cuda and t.dtype in DTYPE_CODE and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
+    layout = _row_layout(t) if t.is_cuda and t.dtype in DTYPE_CODE and t.dim() == 2 else None
+    if layout is None:
         raise TypeError(f"{who}: 2-D float32 / float64 device matrix with unit inner stride required")
-    return int(t.stride(0))
+    return layout[1]
+
+
+def gram_scratch(n, t, device):
+    """the scratch memory ``gram`` needs for a matrix [n, t]: allocate it once where many products of one size follow"""
+    return _scratch(_lib.hip_lib().s3_gram_scratch_bytes(int(n), int(t)), device)
 
 
 def gram(x, mean=None, weight=None, out=None, scratch=None):
@@ -567,16 +586,12 @@ def gram(x, mean=None, weight=None, out=None, scratch=None):
     for name, v in (("mean", mean), ("weight", weight)):
         if v is not None and not (v.is_cuda and v.dtype == pt.float64 and v.numel() == n):
             raise TypeError(f"gram: {name} must be a float64 device vector [{n}]")
-    lib = _lib.hip_lib()
-    need = int(lib.s3_gram_scratch_bytes(n, t))
     if scratch is None:
-        scratch = pt.empty((need + 7) // 8, dtype=pt.float64, device=x.device)
-    elif scratch.numel() * scratch.element_size() < need:
+        scratch = gram_scratch(n, t, x.device)
+    elif scratch.numel() * scratch.element_size() < int(_lib.hip_lib().s3_gram_scratch_bytes(n, t)):
         raise ValueError("gram: scratch too small")
-    out = pt.empty((t, t), dtype=pt.float64, device=x.device) if out is None else out
-    if not (out.dtype == pt.float64 and tuple(out.shape) == (t, t)):
-        raise TypeError("gram: out must be float64 [T, T]")
-    check(lib.s3_gram(C.c_void_p(x.data_ptr()), DTYPE_CODE[x.dtype], n, t, stride, _ptr(mean), _ptr(weight), _ptr(out), _ptr(scratch),
+    out = _out_tensor(out, (t, t), pt.float64, x.device, "gram")
+    check(_lib.hip_lib().s3_gram(C.c_void_p(x.data_ptr()), DTYPE_CODE[x.dtype], n, t, stride, _ptr(mean), _ptr(weight), _ptr(out), _ptr(scratch),
                       _stream()), "s3_gram")
     return out
 
@@ -591,9 +606,7 @@ def tall_gemm(left, b, out=None):
     n = int(b.shape[1])
     if m < 1 or k < 1 or n < 1:
         raise ValueError(f"tall_gemm: empty product [{m}, {k}] x [{k}, {n}]")
-    out = pt.empty((m, n), dtype=pt.float64, device=left.device) if out is None else out
-    if not (out.dtype == pt.float64 and tuple(out.shape) == (m, n)):
-        raise TypeError("tall_gemm: out must be float64 [m, n]")
+    out = _out_tensor(out, (m, n), pt.float64, left.device, "tall_gemm")
     check(_lib.hip_lib().s3_tall_gemm(C.c_void_p(left.data_ptr()), DTYPE_CODE[left.dtype], m, k, stride, _ptr(b), n, _ptr(out), _stream()),
           "s3_tall_gemm")
     return out
@@ -631,9 +644,7 @@ def segment_dft(x, mean, nperseg, hop, n_blk, bre, bim, out=None):
     float64 on the device, rows may be pitched, read where it lies; ``mean`` f64 [N] or None; ``bre`` / ``bim`` f64 [nperseg, n_f]."""
     args = _segment_arguments(x, mean, nperseg, hop, n_blk, bre, bim, "segment_dft")
     shape = (args[2], args[-1], int(n_blk), 2)
-    out = pt.empty(shape, dtype=pt.float64, device=x.device) if out is None else out
-    if not (out.dtype == pt.float64 and tuple(out.shape) == shape):
-        raise TypeError(f"segment_dft: out must be float64 {shape}")
+    out = _out_tensor(out, shape, pt.float64, x.device, "segment_dft")
     check(_lib.hip_lib().s3_segment_dft(*args, _ptr(out), _stream()), "s3_segment_dft")
     return out
 
@@ -645,9 +656,7 @@ def segment_psd(x, mean, nperseg, hop, n_blk, bre, bim, scale, out=None):
     shape = (args[2], args[-1])
     if not (scale.is_cuda and scale.dtype == pt.float64 and scale.numel() == shape[1]):
         raise TypeError(f"segment_psd: scale must be a float64 device vector [{shape[1]}]")
-    out = pt.empty(shape, dtype=pt.float64, device=x.device) if out is None else out
-    if not (out.dtype == pt.float64 and tuple(out.shape) == shape):
-        raise TypeError(f"segment_psd: out must be float64 {shape}")
+    out = _out_tensor(out, shape, pt.float64, x.device, "segment_psd")
     check(_lib.hip_lib().s3_segment_psd(*args, _ptr(scale), _ptr(out), _stream()), "s3_segment_psd")
     return out
 
@@ -691,11 +700,7 @@ def snapshot_major(values, n_comp, n_snapshots, out=None, dtype=None):
     ``numpy.astype(float32)`` does (s3_snapshot_major_as)."""
     dtype = _storage_dtype(dtype, "snapshot_major")
     nc = _batch_values(values, n_comp, n_snapshots, "snapshot_major")
-    if out is None:
-        out = pt.empty((int(n_snapshots), nc, int(n_comp)), dtype=dtype, device=values.device)
-    elif not (out.is_cuda and out.is_contiguous() and out.dtype == dtype and out.numel() == values.numel()
-              and out.device == values.device):
-        raise TypeError(f"snapshot_major: contiguous {dtype} device tensor of the batch's size required as out")
+    out = _out_tensor(out, (int(n_snapshots), nc, int(n_comp)), dtype, values.device, "snapshot_major")
     if dtype == pt.float64:
         check(_lib.hip_lib().s3_snapshot_major(_ptr(values), nc, int(n_comp), int(n_snapshots), _ptr(out), _stream()),
               "s3_snapshot_major")
@@ -821,23 +826,16 @@ class InterpPlan:
         are; dense rows when their length is a multiple of 16 bytes).  Plans with the reference's neighbour counts
         (``k`` = 8 | 26) also take dense rows of any length >= 16 bytes where they lie (element alignment; the persistent
         kernel, s3hip.h)."""
-        if data.dtype not in DTYPE_CODE or data.dim() < 1:
+        layout = _row_layout(data) if data.dtype in DTYPE_CODE else None
+        if layout is None or layout[1] >= 1 << 31:
             return None
+        row_len, in_stride = layout
         epv = 16 // data.element_size()
-        row_len = int(np.prod(data.shape[1:])) if data.dim() > 1 else 1
-        if data.is_contiguous():
-            in_stride = row_len
-        elif data.dim() == 2 and data.stride(1) == 1 and data.stride(0) >= row_len:
-            in_stride = int(data.stride(0))
-        else:
-            return None
-        if in_stride >= 1 << 31:
-            return None
         padded = (row_len + epv - 1) // epv * epv
         if in_stride % epv or in_stride < padded or (data.is_cuda and data.data_ptr() % 16):
             if not (k in (8, 26) and row_len >= epv):
                 return None
-        return row_len, in_stride
+        return layout
 
     @staticmethod
     def supports(k, data):
@@ -1243,5 +1241,4 @@ def topn_leaf(gain, leaf, n_cells, n_top, scratch):
 
 
 def topn_scratch(n_cells, n_top, dev):
-    nbytes = _lib.hip_lib().s3_topn_scratch_bytes(int(n_cells), int(n_top))
-    return pt.empty((nbytes + 7) // 8, dtype=pt.float64, device=dev)
+    return _scratch(_lib.hip_lib().s3_topn_scratch_bytes(int(n_cells), int(n_top)), dev)

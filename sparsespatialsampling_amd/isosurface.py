@@ -18,14 +18,7 @@ import numpy as np
 import torch as pt
 
 from . import hipops
-
-
-def _as_tensor(x, what):
-    if isinstance(x, np.ndarray):
-        return pt.from_numpy(np.ascontiguousarray(x))
-    if not isinstance(x, pt.Tensor):
-        raise TypeError(f"{what} must be a numpy array or a torch tensor, got {type(x).__name__}")
-    return x
+from .arrays import Side, as_tensor, resident
 
 
 class IsoResult:
@@ -56,10 +49,10 @@ class IsoResult:
         """another node field at the vertices: ``g_a + frac (g_b - g_a)`` -> f64 [n, d].  ``other`` is [N_nodes] (one field for
         every snapshot) or [N_nodes, T] (column t for the primitives of snapshot t).  Plain torch, not a hot path."""
         as_numpy = isinstance(self.vertices, np.ndarray)
-        g = _as_tensor(other, "other")
+        g = as_tensor(other, "other")
         if g.dim() not in (1, 2) or int(g.shape[0]) != self.n_nodes or (g.dim() == 2 and int(g.shape[1]) != self.n_snapshots):
             raise ValueError(f"expected a node field [{self.n_nodes}] or [{self.n_nodes}, {self.n_snapshots}], got {tuple(g.shape)}")
-        edges, frac = _as_tensor(self.edges, "edges"), _as_tensor(self.frac, "frac")
+        edges, frac = as_tensor(self.edges, "edges"), as_tensor(self.frac, "frac")
         g = g.to(frac.device, pt.float64)
         a, b = edges[..., 0].long(), edges[..., 1].long()
         if g.dim() == 2:
@@ -76,7 +69,7 @@ class IsoResult:
         point (they have the same bits), ``points[index]`` is the soup again.  Exact, no tolerance."""
         verts, edges, _, _ = self.snapshot(t)
         as_numpy = isinstance(verts, np.ndarray)
-        verts, edges = _as_tensor(verts, "vertices"), _as_tensor(edges, "edges").long()
+        verts, edges = as_tensor(verts, "vertices"), as_tensor(edges, "edges").long()
         d = self.dim
         key = ((edges[..., 0] << 32) | edges[..., 1]).reshape(-1)
         uniq, inverse = pt.unique(key, return_inverse=True)
@@ -90,7 +83,7 @@ class IsoResult:
         ``geometry.geometry_STL_3d.read_stl`` reads it back"""
         if self.dim != 3:
             raise ValueError("STL holds triangles: 3-D only")
-        tri = _as_tensor(self.snapshot(t)[0], "vertices").cpu().numpy().astype("<f4")
+        tri = as_tensor(self.snapshot(t)[0], "vertices").cpu().numpy().astype("<f4")
         if not len(tri):
             raise ValueError(f"snapshot {int(t)} has no triangles")
         wide = tri.astype(np.float64)
@@ -107,11 +100,11 @@ class IsoResult:
 class Isosurface:
     """``nodes`` [N_nodes, d] and ``faces`` [N_cells, 2^d] (the corner nodes of every cell) of a generated grid, d = 2 | 3; numpy or
     torch, host or device.  ``extract`` and ``count`` take node fields [N_nodes] or [N_nodes, T], float32 or float64, numpy or torch,
-    host or device; a window ``field[:, t0:t1]`` of a field that lives on the device is read where it lies.  Results come back on
-    the side (and as the kind of array) the field came from."""
+    host or device; a window ``field[:, t0:t1]`` of a field that lives on the device is read where it lies (``arrays.resident``).
+    Results come back on the side (and as the kind of array) the field came from."""
 
     def __init__(self, nodes, faces):
-        nodes, faces = _as_tensor(nodes, "nodes"), _as_tensor(faces, "faces")
+        nodes, faces = as_tensor(nodes, "nodes"), as_tensor(faces, "faces")
         if nodes.dim() != 2 or int(nodes.shape[1]) not in (2, 3):
             raise ValueError(f"expected nodes [Nn, 2 | 3], got {tuple(nodes.shape)}")
         self.n_nodes, self.dim = int(nodes.shape[0]), int(nodes.shape[1])
@@ -138,8 +131,7 @@ class Isosurface:
         return cls(s_cube.vertices, s_cube.faces)
 
     def _field(self, field, level):
-        as_numpy = isinstance(field, np.ndarray)
-        field = _as_tensor(field, "field")
+        field, side = as_tensor(field, "field"), Side(field)
         shape = tuple(int(v) for v in field.shape)
         if not 1 <= len(shape) <= 2 or shape[0] != self.n_nodes:
             raise ValueError(f"expected a field [{self.n_nodes}] or [{self.n_nodes}, T] on the grid's nodes, got {shape}")
@@ -148,26 +140,17 @@ class Isosurface:
         level = float(level)
         if not np.isfinite(level):
             raise ValueError(f"the level must be finite, got {level!r}")
-        on_host = not field.is_cuda
-        in_place = field.is_cuda and field.dtype in hipops.DTYPE_CODE and field.device == hipops.device() and (
-            field.is_contiguous() or (field.dim() == 2 and field.stride(1) == 1 and field.stride(0) >= field.shape[1]))
-        dev_field = field if in_place else hipops.to_device(field if field.dtype in hipops.DTYPE_CODE else field.to(pt.float64))
-        return dev_field, level, on_host, as_numpy
+        return resident(field), level, side
 
     def count(self, field, level, _count_bytes=hipops.ISO_COUNT_BYTES):
         """the number of primitives of every snapshot (the first pass alone) -> int64 numpy [T]"""
-        dev_field, level, _, _ = self._field(field, level)
+        dev_field, level, _ = self._field(field, level)
         (offsets,) = hipops.iso_extract(dev_field, self._faces, self._nodes, level, count_only=True, count_bytes=_count_bytes)
         return np.diff(offsets)
 
     def extract(self, field, level, _count_bytes=hipops.ISO_COUNT_BYTES):
         """-> ``IsoResult``: the triangles (segments) of ``field == level`` for every snapshot, oriented so that the right-hand normal
         points to ``field < level`` (2-D: ``field >= level`` lies to the left of a segment)"""
-        dev_field, level, on_host, as_numpy = self._field(field, level)
+        dev_field, level, side = self._field(field, level)
         offsets, *arrays = hipops.iso_extract(dev_field, self._faces, self._nodes, level, count_bytes=_count_bytes)
-        if on_host:
-            hipops.synchronize()
-            arrays = [a.cpu() for a in arrays]
-            if as_numpy:
-                arrays = [a.numpy() for a in arrays]
-        return IsoResult(offsets, *arrays, n_nodes=self.n_nodes)
+        return IsoResult(offsets, *(side.back(a) for a in arrays), n_nodes=self.n_nodes)

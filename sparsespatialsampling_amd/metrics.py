@@ -11,6 +11,7 @@ import numpy as np
 import torch as pt
 
 from . import _lib, hipops
+from .arrays import Side, resident
 
 
 def temporal_moments(field: pt.Tensor, unbiased: bool = True):
@@ -18,10 +19,7 @@ def temporal_moments(field: pt.Tensor, unbiased: bool = True):
     device) -> (mean, std) float64 tensors of shape ``field.shape[:-1]`` on the device the field came from"""
     if field.dim() < 2:
         raise ValueError(f"expected a field of shape [N, T] or [N, n_comp, T], got {tuple(field.shape)}")
-    if field.dtype not in hipops.DTYPE_CODE:
-        field = field.to(pt.float64)
-    on_host = not field.is_cuda
-    dev = hipops.to_device(field)
+    dev = resident(field, pitched=False)                    # (the launch below takes dense rows)
     t = int(dev.shape[-1])
     n_rows = int(np.prod(dev.shape[:-1]))
     mean = pt.empty(n_rows, dtype=pt.float64, device=dev.device)
@@ -29,11 +27,8 @@ def temporal_moments(field: pt.Tensor, unbiased: bool = True):
     hipops.check(_lib.hip_lib().s3_row_moments(C.c_void_p(dev.data_ptr()), hipops.DTYPE_CODE[dev.dtype], n_rows, t, t,
                                                1 if unbiased else 0, C.c_void_p(mean.data_ptr()),
                                                C.c_void_p(std.data_ptr()), hipops._stream()), "s3_row_moments")
-    mean, std = mean.reshape(dev.shape[:-1]), std.reshape(dev.shape[:-1])
-    if on_host:
-        hipops.synchronize()
-        return mean.cpu(), std.cpu()
-    return mean, std
+    side = Side(field)
+    return side.back(mean.reshape(dev.shape[:-1])), side.back(std.reshape(dev.shape[:-1]))
 
 
 def temporal_mean_abs_sum(field: pt.Tensor) -> pt.Tensor:
@@ -42,20 +37,14 @@ def temporal_mean_abs_sum(field: pt.Tensor) -> pt.Tensor:
     ``n_comp * T`` values divided by T"""
     if field.dim() != 3:
         raise ValueError(f"expected a field of shape [N, n_comp, T], got {tuple(field.shape)}")
-    if field.dtype not in hipops.DTYPE_CODE:
-        field = field.to(pt.float64)
-    on_host = not field.is_cuda
-    dev = hipops.to_device(field)
+    dev = resident(field, pitched=False)
     n, n_comp, t = (int(v) for v in dev.shape)
     mean = pt.empty(n, dtype=pt.float64, device=dev.device)
     hipops.check(_lib.hip_lib().s3_row_abs_moments(C.c_void_p(dev.data_ptr()), hipops.DTYPE_CODE[dev.dtype], n, n_comp * t,
                                                    n_comp * t, 0, C.c_void_p(mean.data_ptr()), None, hipops._stream()),
                  "s3_row_abs_moments")
     mean *= float(n_comp)                                   # mean over n_comp * T values -> sum over components, mean over T
-    if on_host:
-        hipops.synchronize()
-        return mean.cpu()
-    return mean
+    return Side(field).back(mean)
 
 
 def temporal_std(field: pt.Tensor, unbiased: bool = True) -> pt.Tensor:
@@ -82,7 +71,10 @@ class RunningMoments:
         if n_b == 0:
             return self
         mean_b, std_b = temporal_moments(batch, unbiased=False)
-        m2_b = std_b * std_b * n_b
+        return self.merge(n_b, mean_b, std_b * std_b * n_b)
+
+    def merge(self, n_b: int, mean_b: pt.Tensor, m2_b: pt.Tensor) -> "RunningMoments":
+        """take in ``n_b`` further values per row that have the mean ``mean_b`` and the centred second moment ``m2_b``"""
         if self.count == 0:
             self.count, self._mean, self._m2 = n_b, mean_b, m2_b
             return self

@@ -16,13 +16,12 @@ import numpy as np
 import torch as pt
 
 from . import hipops
+from .arrays import Side, as_tensor, default_neighbors, hilbert_knn, knn_table, resident
+from .metrics import RunningMoments
 
 
 def _default_neighbors(dim, n_centers, n_neighbors):
-    k = (8 if dim == 2 else 26) if n_neighbors is None else int(n_neighbors)     # compute_error_OAT.py:209
-    if k < 1:
-        raise ValueError(f"n_neighbors must be positive, got {k}")
-    return min(k, int(n_centers))
+    return default_neighbors(dim, n_neighbors, n_centers)                         # compute_error_OAT.py:209
 
 
 def _check_clouds(grid_centers, coordinates):
@@ -36,35 +35,6 @@ def _check_clouds(grid_centers, coordinates):
         raise ValueError("the grid has no cells")
 
 
-def _as_tensor(x):
-    return pt.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
-
-
-def _device_field(x):
-    return hipops.to_device(x if x.dtype in hipops.DTYPE_CODE else x.to(pt.float64))
-
-
-def _device_rows(x):
-    """the original rows as the kernel reads them: a snapshot window ``field[:, t0:t1]`` of a resident 2-D device field is taken
-    where it lies (the kernel has a row pitch); anything else becomes a contiguous device tensor"""
-    if (x.is_cuda and x.dtype in hipops.DTYPE_CODE and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1]
-            and x.device == hipops.device()):
-        return x
-    return _device_field(x)
-
-
-def _exact_table(grid_centers, coordinates, k):
-    """neighbour ids (int32) and scikit-learn's distance weights (f64) [N, k] of the points among the cell centres, on the device"""
-    knn = hipops.KnnIndex(grid_centers)
-    try:
-        idx, dist = knn.query(coordinates, k)
-        w = hipops.idw_weights_exact(dist)
-        hipops.synchronize()
-    finally:
-        knn.close()
-    return idx, w
-
-
 class ReconstructionError:
     """Error of the fields on a generated grid against the original CFD fields, measured at the original points.
 
@@ -75,9 +45,9 @@ class ReconstructionError:
 
     The constructor searches the neighbours once; ``update(grid_fields, orig_fields)`` then takes the same snapshots of both
     fields, [Nc, (n_comp,) T_b] and [N, (n_comp,) T_b] (float32 / float64, host or device), batch by batch; a window
-    ``orig[:, t0:t1]`` of a scalar field that lives on the device is read where it lies, other non-contiguous batches are copied
-    once (the small grid batch always is).  The results cover all snapshots seen so far and come back on the side (host /
-    device) the fields came from:
+    ``orig[:, t0:t1]`` of a scalar field that lives on the device is read where it lies (``arrays.resident``), other non-contiguous
+    batches are copied once (the small grid batch always is).  The results cover all snapshots seen so far and come back on the side
+    (host / device) the fields came from:
 
     ``error_time``        [T] f64: ``||d[:, :, t]|| / ||ref[:, :, t]||``, norms over points and components
     ``error_total``       float: ``||d||_F / ||ref||_F``
@@ -87,30 +57,25 @@ class ReconstructionError:
     A zero reference norm divides as torch does (inf / nan)."""
 
     def __init__(self, grid_centers, coordinates, point_scale=None, n_neighbors=None):
-        grid_centers, coordinates = _as_tensor(grid_centers), _as_tensor(coordinates)
+        grid_centers, coordinates = as_tensor(grid_centers, "grid_centers"), as_tensor(coordinates, "coordinates")
         _check_clouds(grid_centers, coordinates)
         self.n_cells, self.n_points = int(grid_centers.shape[0]), int(coordinates.shape[0])
         self.n_neighbors = _default_neighbors(int(coordinates.shape[1]), self.n_cells, n_neighbors)
         if point_scale is not None:
-            point_scale = _as_tensor(point_scale)
+            point_scale = as_tensor(point_scale, "point_scale")
             if point_scale.numel() != self.n_points:
                 raise ValueError(f"point_scale must hold one value per point ({self.n_points}), got {tuple(point_scale.shape)}")
-        self._on_host = not coordinates.is_cuda
+        self._side = Side(coordinates)
         pts = hipops.to_device(coordinates, pt.float64)
-        idx, w = _exact_table(grid_centers, pts, self.n_neighbors)
         # the points are launched in Hilbert order: neighbouring lanes then gather the same few grid rows
-        k = self.n_neighbors
-        self._rows = hipops.spatial_order(pts) if self.n_points else pt.empty(0, dtype=pt.int32, device=pts.device)
-        self._w = hipops.gather_rows(w, self._rows, pt.empty_like(w)) if self.n_points else w
-        self._idx = hipops.gather_rows(idx, self._rows, pt.empty_like(idx)) if self.n_points else idx
+        self._idx, self._w, self._rows = hilbert_knn(grid_centers, pts, self.n_neighbors, exact_weights=True)
         self._scale = None
         if point_scale is not None:
             s = hipops.to_device(point_scale.reshape(-1, 1), pt.float64)
             self._scale = hipops.gather_rows(s, self._rows, pt.empty_like(s)).reshape(-1) if self.n_points else s.reshape(-1)
-        assert self._w.shape == (self.n_points, k)
+        assert self._w.shape == (self.n_points, self.n_neighbors)
         self.n_snapshots = 0
-        self._count = 0                                 # values per point so far: n_comp * n_snapshots
-        self._mean = self._m2 = None
+        self._moments = RunningMoments()                # of |d| per point, over its n_comp * n_snapshots values so far
         self._sum_d, self._sum_ref = [], []             # per batch: [T_b] device tensors
         self._trailing = None                           # n_comp part of the fields' shape
 
@@ -120,7 +85,7 @@ class ReconstructionError:
         return cls(loader.vertices, coordinates, point_scale=point_scale, n_neighbors=n_neighbors)
 
     def update(self, grid_fields, orig_fields) -> "ReconstructionError":
-        grid_fields, orig_fields = _as_tensor(grid_fields), _as_tensor(orig_fields)
+        grid_fields, orig_fields = as_tensor(grid_fields, "grid_fields"), as_tensor(orig_fields, "orig_fields")
         if grid_fields.dim() < 2 or orig_fields.dim() < 2:
             raise ValueError(f"expected fields [Nc, (n_comp,) T] and [N, (n_comp,) T], got {tuple(grid_fields.shape)} and "
                              f"{tuple(orig_fields.shape)}")
@@ -137,38 +102,24 @@ class ReconstructionError:
         if t_b == 0 or (trailing and int(np.prod(trailing)) == 0):
             return self
         self._trailing = trailing
-        self._on_host = not orig_fields.is_cuda
-        grid_dev, orig_dev = _device_field(grid_fields), _device_rows(orig_fields)
+        self._side = Side(orig_fields)
+        grid_dev, orig_dev = resident(grid_fields, pitched=False), resident(orig_fields)    # (the kernel has a row pitch for orig alone)
         mean_b, m2_b, colsum = hipops.recon_error(self._w, self._idx, grid_dev, orig_dev, rows=self._rows, scale=self._scale)
-        n_b = int(np.prod(orig_fields.shape[1:]))
-        if self._count == 0:
-            self._mean, self._m2 = mean_b, m2_b
-        else:                                           # Chan's update, as metrics.RunningMoments
-            n = self._count + n_b
-            delta = mean_b - self._mean
-            self._mean = self._mean + delta * (n_b / n)
-            self._m2 = self._m2 + m2_b + delta * delta * (self._count * n_b / n)
-        self._count += n_b
+        self._moments.merge(int(np.prod(orig_fields.shape[1:])), mean_b, m2_b)
         per_snapshot = colsum.view(2, -1, t_b).sum(1)   # components into their snapshot
         self._sum_d.append(per_snapshot[0])
         self._sum_ref.append(per_snapshot[1])
         self.n_snapshots += t_b
         return self
 
-    def _out(self, t):
-        if self._on_host:
-            hipops.synchronize()
-            return t.cpu()
-        return t
-
     def _need_data(self):
-        if self._count == 0:
+        if self._moments.count == 0:
             raise RuntimeError("ReconstructionError: no snapshots yet, call update() first")
 
     @property
     def error_time(self) -> pt.Tensor:
         self._need_data()
-        return self._out(pt.cat(self._sum_d).sqrt() / pt.cat(self._sum_ref).sqrt())
+        return self._side.back(pt.cat(self._sum_d).sqrt() / pt.cat(self._sum_ref).sqrt())
 
     @property
     def error_total(self) -> float:
@@ -178,28 +129,24 @@ class ReconstructionError:
     @property
     def error_space_mean(self) -> pt.Tensor:
         self._need_data()
-        return self._out(self._mean)
+        return self._side.back(self._moments.mean())
 
     @property
     def error_space_std(self) -> pt.Tensor:
         self._need_data()
-        return self._out((self._m2 / (self._count - 1)).sqrt())
+        return self._side.back(self._moments.std())
 
 
 def reconstruct(grid_centers, grid_fields, coordinates, n_neighbors=None) -> pt.Tensor:
     """the fitted field itself, ``KNeighborsRegressor(n_neighbors, weights="distance").fit(grid_centers, grid_fields)
     .predict(coordinates)`` as float64 [N, ...]: the unfused path (``hipops.interp`` with the exact weights), for cases small
     enough to hold N x T values -- a plot of the fitted field.  Returned on the side ``grid_fields`` came from."""
-    grid_centers, coordinates, grid_fields = _as_tensor(grid_centers), _as_tensor(coordinates), _as_tensor(grid_fields)
+    grid_centers, coordinates = as_tensor(grid_centers, "grid_centers"), as_tensor(coordinates, "coordinates")
+    grid_fields = as_tensor(grid_fields, "grid_fields")
     _check_clouds(grid_centers, coordinates)
     if grid_fields.dim() < 1 or int(grid_fields.shape[0]) != int(grid_centers.shape[0]):
         raise ValueError(f"expected one row of grid_fields per cell centre ({int(grid_centers.shape[0])}), got "
                          f"{tuple(grid_fields.shape)}")
     k = _default_neighbors(int(coordinates.shape[1]), grid_centers.shape[0], n_neighbors)
-    on_host = not grid_fields.is_cuda
-    idx, w = _exact_table(grid_centers, hipops.to_device(coordinates, pt.float64), k)
-    out = hipops.interp(w, idx, _device_field(grid_fields))
-    if on_host:
-        hipops.synchronize()
-        return out.cpu()
-    return out
+    idx, w = knn_table(grid_centers, hipops.to_device(coordinates, pt.float64), k, exact_weights=True)
+    return Side(grid_fields).back(hipops.interp(w, idx, resident(grid_fields, pitched=False)))

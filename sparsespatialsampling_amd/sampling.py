@@ -22,14 +22,7 @@ import numpy as np
 import torch as pt
 
 from . import hipops
-
-
-def _as_tensor(x, what):
-    if isinstance(x, np.ndarray):
-        return pt.from_numpy(np.ascontiguousarray(x))
-    if not isinstance(x, pt.Tensor):
-        raise TypeError(f"{what} must be a numpy array or a torch tensor, got {type(x).__name__}")
-    return x
+from .arrays import Side, as_tensor, resident
 
 
 # ---- point sets (host only) -------------------------------------------------------------------------------------------------
@@ -87,12 +80,12 @@ class Probe:
     ``cell_ids`` (int32 [Nq], -1: no cell) and ``inside`` (bool [Nq]) come back in the caller's order, on the side (and as the kind
     of array) the points came from.  ``sample`` takes fields [rows, (n_comp,) T] (``[rows]``: one snapshot; rows = cells for
     ``mode="cell"``, nodes for ``mode="linear"``), float32 or float64, numpy or torch, host or device; a window ``field[:, t0:t1]``
-    of a scalar field that lives on the device is read where it lies.  Results are float64 [Nq, (n_comp,) T] on the side the field
-    came from, NaN where ``inside`` is False."""
+    of a scalar field that lives on the device is read where it lies (``arrays.resident``).  Results are float64 [Nq, (n_comp,) T] on
+    the side the field came from, NaN where ``inside`` is False."""
 
     def __init__(self, centers, levels, width, points, nodes=None, faces=None):
-        self._numpy = isinstance(points, np.ndarray)
-        points, centers, levels = _as_tensor(points, "points"), _as_tensor(centers, "centers"), _as_tensor(levels, "levels")
+        points, self._side = as_tensor(points, "points"), Side(points)
+        centers, levels = as_tensor(centers, "centers"), as_tensor(levels, "levels")
         if centers.dim() != 2 or int(centers.shape[1]) not in (2, 3):
             raise ValueError(f"expected centers [Nc, 2 | 3], got {tuple(centers.shape)}")
         self.n_cells, self.dim = int(centers.shape[0]), int(centers.shape[1])
@@ -103,12 +96,11 @@ class Probe:
         if (nodes is None) != (faces is None):
             raise ValueError("nodes and faces go together")
         self.n_points = int(points.shape[0])
-        self._on_host = not points.is_cuda
         self._index = hipops.cell_index(hipops.to_device(centers, pt.float64), hipops.to_device(levels.reshape(-1), pt.int32), width)
         self._points = hipops.to_device(points, pt.float64)
         self._faces, self.n_nodes = None, None
         if faces is not None:
-            faces, nodes = _as_tensor(faces, "faces"), _as_tensor(nodes, "nodes")
+            faces, nodes = as_tensor(faces, "faces"), as_tensor(nodes, "nodes")
             if tuple(faces.shape) != (self.n_cells, 1 << self.dim) or faces.is_floating_point():
                 raise ValueError(f"expected integer faces [{self.n_cells}, {1 << self.dim}], got {tuple(faces.shape)} {faces.dtype}")
             if nodes.dim() != 2 or int(nodes.shape[1]) != self.dim:
@@ -137,19 +129,13 @@ class Probe:
             raise ValueError("the grid has not been generated yet: call execute_grid_generation() first")
         return cls(s_cube.centers, s_cube.levels, float(s_cube.size_initial_cell), points, nodes=s_cube.vertices, faces=s_cube.faces)
 
-    def _back(self, t):
-        if self._on_host:
-            hipops.synchronize()
-            t = t.cpu()
-        return t.numpy() if self._numpy and self._on_host else t
-
     @property
     def cell_ids(self):
-        return self._back(self._ids)
+        return self._side.back(self._ids)
 
     @property
     def inside(self):
-        return self._back(self._ids >= 0)
+        return self._side.back(self._ids >= 0)
 
     def sample(self, field, mode="cell"):
         """[rows, (n_comp,) T] -> float64 [Nq, (n_comp,) T]"""
@@ -157,29 +143,16 @@ class Probe:
             raise ValueError(f"unknown mode {mode!r}, expected one of {sorted(hipops.SAMPLE_MODES)}")
         if mode == "linear" and self._faces is None:
             raise ValueError("mode 'linear' blends the corner values of a cell: build the Probe with nodes and faces")
-        as_numpy = isinstance(field, np.ndarray)
-        field = _as_tensor(field, "field")
+        field, side = as_tensor(field, "field"), Side(field)
         shape = tuple(int(v) for v in field.shape)
         n_rows = self.n_cells if mode == "cell" else self.n_nodes
         if not 1 <= len(shape) <= 3 or shape[0] != n_rows:
             raise ValueError(f"{mode}: expected a field [{n_rows}, (n_comp,) T] on the grid's {'cells' if mode == 'cell' else 'nodes'}, got {shape}")
         if 0 in shape:
             raise ValueError(f"{mode}: empty field {shape}")
-        on_host = not field.is_cuda
-        dev_field = field if self._reads_in_place(field) else hipops.to_device(field if field.dtype in hipops.DTYPE_CODE else field.to(pt.float64))
+        dev_field = resident(field)
         if self.n_points:
             res = hipops.cell_sample(self._ids, dev_field, mode, rows=self._rows, index=self._index, points=self._points, faces=self._faces)
         else:
             res = pt.empty((0,) + shape[1:], dtype=pt.float64, device=dev_field.device)
-        res = res.view((self.n_points,) + shape[1:])
-        if on_host:
-            hipops.synchronize()
-            res = res.cpu()
-        return res.numpy() if as_numpy else res
-
-    @staticmethod
-    def _reads_in_place(x):
-        """a contiguous device field, or a snapshot window ``field[:, t0:t1]`` of a resident 2-D one (the kernel has a row pitch)"""
-        if not (x.is_cuda and x.dtype in hipops.DTYPE_CODE and x.device == hipops.device()):
-            return False
-        return x.is_contiguous() or (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1])
+        return side.back(res.view((self.n_points,) + shape[1:]))

@@ -30,6 +30,7 @@ import numpy as np
 import torch as pt
 
 from . import hipops
+from .arrays import Side, resident_matrix
 from .dmd import _check_arguments
 
 LD = np.longdouble
@@ -119,13 +120,6 @@ def psd_scale(w, dt, n_blk, k, nperseg, scaling):
     return (base * one_sided_factor(k, nperseg).astype(LD) / LD(n_blk)).astype(np.float64)
 
 
-def _device_rows(data, n_cells, n_comp, t):
-    """the data on the device as a 2-D matrix [N rows, T], read where it lies when it is there already"""
-    dev = hipops.device()
-    d = data if data.is_cuda and data.device == dev else hipops.to_device(data)
-    return d.reshape(n_cells * n_comp, t) if n_comp is not None else d
-
-
 def welch(data, dt, nperseg=None, noverlap=None, window="hann", detrend="constant", scaling="density", frequencies=None):
     """Power spectral density of every row of ``data`` [N, T] or [N, n_comp, T] (float32 or float64, host or device; a 2-D matrix may
     be pitched) by Welch's method, as ``scipy.signal.welch(data, fs=1/dt, ...)`` returns it: defaults ``nperseg = min(256, T)``,
@@ -141,17 +135,16 @@ def welch(data, dt, nperseg=None, noverlap=None, window="hann", detrend="constan
         raise ValueError(f"scaling must be 'density' or 'spectrum', got {scaling!r}")
     k = _frequencies(frequencies, nperseg)
     w = _window(window, nperseg)
-    d2 = _device_rows(data, n_cells, n_comp, t)                               # (HipUnavailableError without a device)
+    d2 = resident_matrix(data, n_cells, n_comp, t)                            # (HipUnavailableError without a device)
     bre, bim, w = segment_matrix(nperseg, w, detrend, k)
     scale = psd_scale(w, float(dt), n_blk, k, nperseg, scaling)
     mean = hipops.row_means(d2) if detrend == "constant" else None
     psd = hipops.segment_psd(d2, mean, nperseg, hop, n_blk, hipops.to_device(bre), hipops.to_device(bim), hipops.to_device(scale))
     psd = psd.reshape(tuple(data.shape[:-1]) + (len(k),))
     freq = pt.from_numpy(k.astype(np.float64) / (nperseg * float(dt)))
-    if data.is_cuda:
-        hipops.synchronize()                                                  # (the caller's matrix is not kept alive)
-        return freq.to(psd.device), psd
-    return freq, pt.from_numpy(hipops.to_host(psd))
+    hipops.synchronize()                                                      # (the caller's matrix is not kept alive)
+    side = Side(data)
+    return side.back(freq), side.back(psd)
 
 
 def _spod_small(grams, kappa):
@@ -200,7 +193,7 @@ class SPOD:
         k = _frequencies(frequencies, nperseg)
         w = _window(window, nperseg)
         self.dt, self.nperseg, self.noverlap, self.n_blocks = float(dt), nperseg, noverlap, n_blk
-        self._on_host = not data.is_cuda
+        self._side = Side(data)
         self._shape = tuple(data.shape)
         n_rows = n_cells * (n_comp or 1)
         need = 16 * n_rows * len(k) * n_blk
@@ -208,7 +201,7 @@ class SPOD:
         if need > free:
             raise ValueError(f"SPOD: the coefficients of {n_rows} rows x {len(k)} frequencies x {n_blk} segments take {need} bytes "
                              f"({need / 2 ** 30:.1f} GiB), the device has {free} free; keep fewer bins with frequencies=")
-        d2 = _device_rows(data, n_cells, n_comp, t)
+        d2 = resident_matrix(data, n_cells, n_comp, t)
         bre, bim, w = segment_matrix(nperseg, w, "constant" if detrend == "constant" else None, k)
         wl = w.astype(LD)
         self._kappa = float(LD(self.dt) / ((wl * wl).sum() * LD(n_blk)))
@@ -224,27 +217,24 @@ class SPOD:
         n_f, width = len(k), 2 * n_blk
         flat = self._coef.view(n_rows, n_f * width)
         grams = pt.empty((n_f, width, width), dtype=pt.float64, device=d2.device)
-        scratch = pt.empty((int(hipops._lib.hip_lib().s3_gram_scratch_bytes(n_rows, width)) + 7) // 8, dtype=pt.float64, device=d2.device)
+        scratch = hipops.gram_scratch(n_rows, width, d2.device)
         for f in range(n_f):                                                  # the pitched [N, 2 n_blk] matrix of frequency f, as it stands
             hipops.gram(flat[:, f * width:(f + 1) * width], None, weight, out=grams[f], scratch=scratch)
         self._lam, self._theta = _spod_small(pt.from_numpy(hipops.to_host(grams)), self._kappa)
         del grams, scratch, weight
 
-    def _out(self, x):
-        return x if self._on_host else x.to(hipops.device())
-
     @property
     def frequency(self):
-        return self._out(self._frequency)
+        return self._side.back(self._frequency)
 
     @property
     def eigvals(self):
-        return self._out(self._lam * self._factor[:, None])
+        return self._side.back(self._lam * self._factor[:, None])
 
     def energy_fraction(self):
         """share of each mode in its frequency's total [n_f, n_blk]"""
         total = self._lam.sum(1, keepdim=True)
-        return self._out(self._lam / pt.where(total > 0, total, pt.ones_like(total)))
+        return self._side.back(self._lam / pt.where(total > 0, total, pt.ones_like(total)))
 
     def modes(self, i_freq, n_modes=None):
         """the leading ``n_modes`` (None: all n_blk) SPOD modes of frequency ``i_freq``: ``sqrt(kappa) Q_f Theta Lambda^-1/2``, complex128
@@ -263,4 +253,4 @@ class SPOD:
         flat = self._coef.view(self._coef.shape[0], -1)
         out = hipops.tall_gemm(flat[:, i_freq * width:(i_freq + 1) * width], hipops.to_device(rhs))
         z = pt.view_as_complex(out.reshape(-1, n_modes, 2)).reshape(self._shape[:-1] + (n_modes,))
-        return z.cpu() if self._on_host else z
+        return self._side.back(z)

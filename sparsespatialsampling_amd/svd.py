@@ -43,6 +43,7 @@ from typing import Tuple
 import torch as pt
 
 from . import _lib, hipops, metrics
+from .arrays import Side
 
 
 def optimal_rank(s: pt.Tensor, n_rows: int, n_cols: int) -> int:
@@ -181,8 +182,8 @@ def compute_svd(data_matrix: pt.Tensor, cell_area: pt.Tensor, rank: int = None) 
     shape = tuple(data_matrix.shape)
     if len(shape) not in (2, 3):
         raise ValueError(f"expected [N_cells, N_snapshots] or [N_cells, N_dims, N_snapshots], got {shape}")
-    on_host = not data_matrix.is_cuda
-    x = hipops.to_device(data_matrix if data_matrix.dtype == pt.float64 else data_matrix.to(pt.float64))
+    side = Side(data_matrix)
+    x = hipops.to_device(data_matrix if data_matrix.dtype == pt.float64 else data_matrix.to(pt.float64))    # (float32 is widened too)
     area = hipops.to_device(cell_area, pt.float64).reshape(-1)
     n_cells, t = shape[0], shape[-1]
     if len(shape) == 3:
@@ -202,8 +203,7 @@ def compute_svd(data_matrix: pt.Tensor, cell_area: pt.Tensor, rank: int = None) 
     u = centered_gemm(x2, mean, b)                            # (X - mean 1^T) B; the sqrt(area) factors cancel
     if len(shape) == 3:
         u = u.reshape(n_cells, shape[1], r)
-    s, v = s.to(x2.device), v.to(x2.device)
-    return (s.cpu(), u.cpu(), v.cpu()) if on_host else (s, u, v)
+    return side.back(s), side.back(u), side.back(v)
 
 
 def write_svd_s_cube_to_file(field_names, load_dir: str, file_name: str, new_file: bool, n_modes: int = None, rank=None,

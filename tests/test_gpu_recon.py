@@ -204,10 +204,10 @@ def test_batchings_agree_with_one_another(batched, pair):
 def test_window_of_a_resident_field_is_read_where_it_lies(cloud):
     """``orig[:, t0:t1]`` of a [N, T] device field reaches the kernel as a pitched view (no copy of N x T_b values) and gives
     the bits of the contiguous copy"""
-    from sparsespatialsampling_amd import reconstruction
+    from sparsespatialsampling_amd import arrays
     c, x, f, o = dev(cloud["c"]), dev(cloud["x"]), dev(cloud["f"]), dev(cloud["o"])
     window = o[:, 3:12]
-    assert not window.is_contiguous() and reconstruction._device_rows(window).data_ptr() == window.data_ptr()
+    assert not window.is_contiguous() and arrays.resident(window).data_ptr() == window.data_ptr()
     lies = ReconstructionError(c, x, point_scale=dev(cloud["s"])).update(f[:, 3:12], window)
     copy = ReconstructionError(c, x, point_scale=dev(cloud["s"])).update(f[:, 3:12].contiguous(), window.contiguous())
     for a, b in zip(results(lies), results(copy)):
