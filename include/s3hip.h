@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 15
+#define S3_ABI_VERSION 16
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -448,6 +448,58 @@ int s3_cell_sample(int mode, const int32_t *d_cell /*[nq]*/, int64_t nq, const i
                    const double *d_points /*[nq,dim]*/, const double *d_centers /*[n_cells,dim]*/, const int32_t *d_levels /*[n_cells]*/,
                    double width, const int32_t *d_faces /*[n_cells,2^dim]*/, int64_t n_cells, double *d_out, int64_t out_stride,
                    s3_stream stream);
+
+/* ---- streamlines and pathlines of node velocity fields (csrc/trace.hip; no counterpart in the reference) ----
+ * The grid, its index and its lattice are those of s3_cell_index; the velocity lives on the grid NODES: d_field rows [dim][row_len] f32 or
+ * f64 (dtype: S3_DTYPE_*) with pitch in_stride ELEMENTS (0 = dim * row_len), read where they lie, component c of node n at column t at
+ * d_field[n * in_stride + c * row_len + t].  One lane per particle carries the whole loop.  This text is normative.
+ *   velocity    at a position x in column t: the cell s3_cell_locate gives x (floored f64 lattice quotient, range test before the
+ *               integer conversion, half-open cells, the upper cell on a face) and the S3_SAMPLE_LINEAR blend of its 2^dim corner rows
+ *               (the xi clamp, one rounding per axis in a weight, the f64 fma chain over the corners in the order of d_faces from 0):
+ *               the bits s3_cell_sample returns at x.
+ *   time        S3_TRACE_PATH only.  A snapshot interval [c, c+1] takes `substeps` RK4 steps; the stage s in {0, 1/2, 1} of step m sits
+ *               at p / (2 substeps) from column c, with the integer p = 2m + 2s forward and 2 substeps - (2m + 2s) backward.
+ *                   p < 2 substeps: n = c, theta = (double) p / (double) (2 substeps)     p = 2 substeps: n = c + 1, theta = 0
+ *                   where that n is the last column: n = row_len - 2, theta = 1
+ *                   v(x) = fma(theta, v_{n+1}(x) - v_n(x), v_n(x))  per component, both blends in the same cell
+ *               (n = floor(tau), theta = tau - n for tau = c + p / (2 substeps), without the rounding of forming tau).  Forward the
+ *               intervals run c = 0 .. row_len - 2, backward c = row_len - 2 .. 0.
+ *   one step    k1 = v(x); x2 = fma(dt/2, k1, x); k2 = v(x2); x3 = fma(dt/2, k2, x); k3 = v(x3); x4 = fma(dt, k3, x); k4 = v(x4);
+ *               x' = fma(dt/6, (k1 + k4) + 2 (k2 + k3), x)  per component, in f64 as written.
+ *   step size   S3_TRACE_STEP_TIME: dt = direction * step (pathlines: step = snapshot spacing / substeps, formed by the caller).
+ *               S3_TRACE_STEP_CELL (streamlines only): dt = direction * ((step * h) / |k1|) with h the edge of the cell of x, step the
+ *               CFL number and |k1| = sqrt((k1_0 k1_0 + k1_1 k1_1) + k1_2 k1_2), every product and sum rounded on its own.
+ *   particles   S3_TRACE_STREAM: (seed, column) pairs, n_seeds * row_len of them; column t of the field is a steady velocity of its own;
+ *               n_steps steps each.  S3_TRACE_PATH: the seeds; (row_len - 1) * substeps steps each (n_steps and every are not read).
+ *   the end     the seed is located first; one that no cell holds has length 0, status S3_TRACE_SEED_OUTSIDE and only NaN rows.  A step
+ *               is accepted only when x2, x3, x4 and x' all have a cell (the cell of x' is the next step's first locate, done once);
+ *               otherwise the particle stays at x with status S3_TRACE_LEFT and x' is not recorded: a path holds points inside the grid
+ *               only.  A cell whose id, level or one of whose corner ids is out of range counts as missing: nothing is loaded through
+ *               them.  S3_TRACE_STEP_CELL with |k1| zero or not finite: S3_TRACE_STAGNANT.  All steps taken: S3_TRACE_DONE.
+ *   output      d_paths f64: S3_TRACE_STREAM [n_seeds][row_len][n_out][dim], n_out = 1 + n_steps / every: row 0 the seed, row r the
+ *               position after r * every accepted steps; S3_TRACE_PATH [n_seeds][row_len][dim]: the position at every snapshot, the
+ *               seed in column 0 forward and in column row_len - 1 backward.  d_length (rows written, in the order they were written),
+ *               d_status, d_cell (the cell of the last position, -1 for a seed outside): int32 [n_seeds][row_len] | [n_seeds].  Rows
+ *               past the length are NaN.
+ *   launch      slot j of the launch takes seed d_order[j] (NULL: seed j; pathlines: the order of s3_spatial_order).  Streamline
+ *               lanes run the column fastest.  Terminated lanes idle; no compaction.
+ * A lane remembers its leaf and skips the binary search for a stage point whose lattice index lies in the leaf's aligned box, an integer
+ * test on the same quotient: the bits do not depend on it, nor on row_len, the order of the seeds, d_order, `every`, the element type
+ * (an f32 field gives the bits of its f64 copy) or the run.  No atomics, no LDS. */
+#define S3_TRACE_STREAM 0
+#define S3_TRACE_PATH 1
+#define S3_TRACE_STEP_TIME 0
+#define S3_TRACE_STEP_CELL 1
+#define S3_TRACE_DONE 0
+#define S3_TRACE_LEFT 1
+#define S3_TRACE_STAGNANT 2
+#define S3_TRACE_SEED_OUTSIDE 3
+int s3_trace(int mode, const uint64_t *d_starts, const uint64_t *d_ends, const int32_t *d_ids, int64_t n_cells, int dim, int depth,
+             const double *h_origin /*[3]*/, double h_min, const double *d_centers /*[n_cells,dim]*/, const int32_t *d_levels /*[n_cells]*/,
+             double width, const int32_t *d_faces /*[n_cells,2^dim]*/, const void *d_field, int dtype, int64_t row_len, int64_t in_stride,
+             int64_t n_nodes, const double *d_seeds /*[n_seeds,dim]*/, int64_t n_seeds, const int32_t *d_order /*[n_seeds] or NULL*/,
+             int64_t n_steps, int substeps, int every, int step_rule, double step /*dt or cfl, > 0*/, int direction /*1 | -1*/,
+             double *d_paths, int32_t *d_length, int32_t *d_status, int32_t *d_cell, s3_stream stream);
 
 /* ---- isosurfaces (3-D) and contour lines (2-D) of node fields by marching simplices (csrc/iso.hip; no counterpart in the reference) ----
  * Inputs: d_nodes [n_nodes][dim] f64; d_faces [n_cells][2^dim] int32 in the corner order above ((-,-), (-,+), (+,+), (+,-) in 2-D;

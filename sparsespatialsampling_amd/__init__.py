@@ -20,7 +20,7 @@ if _os.environ.get("S3_KEEP_RUNTIME_PINNING") != "1":
 
 from .version import __version__
 
-__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "Probe", "Isosurface", "IsoResult", "__version__"]
+__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "Probe", "Isosurface", "IsoResult", "Tracer", "Paths", "__version__"]
 
 
 def __getattr__(name):
@@ -43,4 +43,7 @@ def __getattr__(name):
     if name in ("Isosurface", "IsoResult"):
         from . import isosurface
         return getattr(isosurface, name)
+    if name in ("Tracer", "Paths"):
+        from . import tracing
+        return getattr(tracing, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -26,7 +26,7 @@ class S3HipError(RuntimeError):
 
 _hip = None
 _topo = None
-ABI_VERSION = 15         # S3_ABI_VERSION of include/s3hip.h this file was written against
+ABI_VERSION = 16         # S3_ABI_VERSION of include/s3hip.h this file was written against
 _REBUILD = "python -c 'import __graft_entry__ as g; g.build()'"
 
 c_i64, c_i32, c_int, c_dbl, c_vp = C.c_int64, C.c_int32, C.c_int, C.c_double, C.c_void_p
@@ -90,6 +90,8 @@ HIP_SIGNATURES = {
     "s3_cell_locate": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_dbl, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "s3_cell_sample": (c_int, [c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i64,
                                c_vp, c_i64, c_vp]),
+    "s3_trace": (c_int, [c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_dbl, c_vp, c_vp, c_dbl, c_vp, c_vp, c_int, c_i64, c_i64, c_i64,
+                         c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "s3_iso_count": (c_int, [c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp]),
     "s3_iso_emit": (c_int, [c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "s3_interp": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_i64, c_i64, c_vp, c_vp]),

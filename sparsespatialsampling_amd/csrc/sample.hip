@@ -29,6 +29,7 @@
 // w_m: t = (s_m0 > 0 ? xi_0 : 1 - xi_0), then per further axis t = s_ma > 0 ? t * xi_a : fma(-xi_a, t, t) (one rounding per axis);
 // out = f64 fma chain over the corners m = 0 .. 2^d - 1 from 0, independent of row_len, VEC, LP and n_comp.  No atomics on
 // floating-point values: the same inputs give the same bits on every run.
+#include "cell_lookup.h"
 #include "point_slots.h"
 #include "typed_rows.h"
 
@@ -41,20 +42,12 @@ namespace {
 constexpr int SAMPLE_THREADS = POINT_THREADS;
 constexpr int SAMPLE_BLOCK = 256;       // queries per workgroup
 
-struct Lattice {
-    double origin[3];
-    double h_min;
-    int depth;                          // L
-};
-
 // what the one-workgroup reduction over the cells leaves for the host
 struct LatticeSeed {
     int lmin, lmax;
     long long first_coarse;             // the first cell of level lmin
     double lo[3];
 };
-
-__host__ __device__ inline double cell_size(double width, int level) { return width / (double)(1ull << level); }
 
 // ---- index ----------------------------------------------------------------------------------------------------------------
 template <int DIM>
@@ -108,15 +101,6 @@ lattice_seed_kernel(const double *__restrict__ c, const int32_t *__restrict__ le
     }
 }
 
-template <int DIM>
-__device__ __forceinline__ uint64_t morton_key(const uint64_t (&i)[DIM], int depth) {
-    uint64_t key = 0;
-    for (int b = 0; b < depth; ++b)
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) key |= ((i[a] >> b) & 1ull) << (b * DIM + a);
-    return key;
-}
-
 // counts[0]: cells with an anchor more than 1e-6 lattice units off an integer (or outside the lattice); counts[1]: misaligned anchors
 template <int DIM>
 __global__ void __launch_bounds__(256)
@@ -166,37 +150,17 @@ cell_locate_kernel(const uint64_t *__restrict__ starts, const uint64_t *__restri
     const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (j >= nq) return;
     const int64_t q = rows ? (int64_t)rows[j] : j;
-    const double extent = (double)(1ull << lat.depth);
-    uint64_t i[DIM];
-    bool inside = true;
+    double p[DIM];
 #pragma unroll
-    for (int a = 0; a < DIM; ++a) {
-        const double t = floor((x[q * DIM + a] - lat.origin[a]) / lat.h_min);
-        const bool ok = t >= 0.0 && t < extent;                                 // false for NaN, +-inf and whatever lies outside
-        inside &= ok;
-        i[a] = ok ? (uint64_t)t : 0;
-    }
+    for (int a = 0; a < DIM; ++a) p[a] = x[q * DIM + a];
+    uint64_t i[DIM];
     int32_t id = -1;
-    if (inside) {
-        const uint64_t key = morton_key<DIM>(i, lat.depth);
-        int64_t lo = 0, hi = n_cells;                                           // upper bound: the first range that starts past the key
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (starts[mid] <= key) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo > 0 && key < ends[lo - 1]) id = ids[lo - 1];
-    }
+    if (lattice_index<DIM>(lat, p, i)) id = search_leaf(starts, ends, ids, n_cells, morton_key<DIM>(i, lat.depth));
     out[q] = id;
 }
 
 // ---- sample ---------------------------------------------------------------------------------------------------------------
-// corner m of a cell in the order `faces` lists them: 2-D (-,-), (-,+), (+,+), (+,-); 3-D that order at z+, then at z-
-__device__ __forceinline__ bool corner_plus(int m, int axis) {
-    const int q = m & 3;
-    return axis == 0 ? q >= 2 : axis == 1 ? (q == 1 || q == 2) : m < 4;
-}
-
+// (the corner order of `faces` and the weight chain: corner_plus, local_xi and corner_weight of csrc/cell_lookup.h)
 struct SampleArgs {
     const int32_t *cell;
     int64_t nq;
@@ -248,16 +212,11 @@ cell_sample_kernel(const int32_t *__restrict__ cell, int64_t nq, const int32_t *
                     if (id >= 0 && id < n_field_rows) row = (int32_t)id;
                 } else if (id >= 0 && id < n_cells) {
                     const double h = cell_size(width, level[id]);
-                    double w = 0.0;
+                    double xi[DIM];
 #pragma unroll
-                    for (int a = 0; a < DIM; ++a) {
-                        double xi = (x[q * DIM + a] - (centers[id * DIM + a] - h / 2)) / h;
-                        xi = fmin(fmax(xi, 0.0), 1.0);
-                        if (a == 0) w = corner_plus(m, 0) ? xi : 1.0 - xi;
-                        else w = corner_plus(m, a) ? w * xi : fma(-xi, w, w);
-                    }
+                    for (int a = 0; a < DIM; ++a) xi[a] = local_xi(x[q * DIM + a], centers[id * DIM + a], h);
                     const int32_t node = faces[id * NCORN + m];
-                    s_w[e] = w;
+                    s_w[e] = corner_weight<DIM>(xi, m);
                     if (node >= 0 && node < n_field_rows) row = node;
                 }
                 s_i[e] = row;
@@ -426,10 +385,7 @@ int s3_cell_locate(const uint64_t *d_starts, const uint64_t *d_ends, const int32
     S3_REQUIRE(depth >= 0 && dim * depth <= 63 && h_origin && h_min > 0.0, "s3_cell_locate: bad lattice (depth %d)", depth);
     if (nq == 0) return S3_OK;
     S3_REQUIRE(d_starts && d_ends && d_ids && d_points && d_out, "s3_cell_locate: null array");
-    Lattice lat{};
-    for (int a = 0; a < dim; ++a) lat.origin[a] = h_origin[a];
-    lat.h_min = h_min;
-    lat.depth = depth;
+    const Lattice lat = make_lattice(h_origin, dim, h_min, depth);
     hipStream_t st = as_stream(stream);
     if (dim == 2)
         cell_locate_kernel<2><<<grid_for(nq, 256), 256, 0, st>>>(d_starts, d_ends, d_ids, n_cells, lat, d_points, nq, d_rows, d_out);

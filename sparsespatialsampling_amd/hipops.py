@@ -469,6 +469,83 @@ def cell_sample(ids, field, mode="cell", rows=None, out=None, index=None, points
     return out
 
 
+TRACE_STEP_RULES = {"time": 0, "cell": 1}                                           # S3_TRACE_STEP_* (s3hip.h)
+TRACE_STATUS = {"DONE": 0, "LEFT": 1, "STAGNANT": 2, "SEED_OUTSIDE": 3}             # S3_TRACE_* (s3hip.h)
+
+
+def _trace(mode, who, index, faces, velocity, seeds, order, n_steps, substeps, every, rule, step, direction, paths, length, status, cells):
+    if not isinstance(index, CellIndex):
+        raise TypeError(f"{who}: index must be what cell_index returned")
+    dim, n_cells = index.dim, index.n_cells
+    if not (isinstance(faces, pt.Tensor) and faces.is_cuda and faces.dtype == pt.int32 and faces.is_contiguous()
+            and tuple(faces.shape) == (n_cells, 1 << dim)):
+        raise TypeError(f"{who}: faces must be a contiguous int32 device tensor [{n_cells}, {1 << dim}]")
+    if not (isinstance(velocity, pt.Tensor) and velocity.is_cuda and velocity.dtype in DTYPE_CODE and velocity.dim() == 3
+            and velocity.is_contiguous()):
+        raise TypeError(f"{who}: velocity must be a contiguous float32 / float64 device tensor [n_nodes, {dim}, T]")
+    n_nodes, n_comp, t = (int(v) for v in velocity.shape)
+    if n_comp != dim:
+        raise ValueError(f"{who}: a velocity on a {dim}-D grid has {dim} components, got {n_comp}")
+    if n_nodes < 1 or t < (2 if mode else 1):
+        raise ValueError(f"{who}: velocity {tuple(velocity.shape)} has too few {'snapshots for a pathline (two at least)' if n_nodes else 'nodes'}")
+    n_seeds = _query_points(seeds, dim, who)
+    _launch_rows(order, n_seeds, who)
+    if rule not in TRACE_STEP_RULES:
+        raise ValueError(f"{who}: unknown step rule {rule!r}, expected one of {sorted(TRACE_STEP_RULES)}")
+    step = float(step)
+    if not (np.isfinite(step) and step > 0.0):
+        raise ValueError(f"{who}: the step ({'cfl' if rule == 'cell' else 'dt'}) must be positive and finite, got {step!r}")
+    if direction not in (1, -1):
+        raise ValueError(f"{who}: direction must be 1 or -1, got {direction!r}")
+    if mode:
+        if int(substeps) < 1:
+            raise ValueError(f"{who}: substeps must be positive, got {substeps}")
+        shape, n_out = (n_seeds,), t
+    else:
+        if int(n_steps) < 1 or int(every) < 1:
+            raise ValueError(f"{who}: n_steps and every must be positive, got {n_steps} and {every}")
+        if n_seeds * t >= 1 << 31:
+            raise ValueError(f"{who}: {n_seeds} seeds x {t} columns are too many particles for one launch")
+        shape, n_out = (n_seeds, t), 1 + int(n_steps) // int(every)
+    paths = _out_tensor(paths, shape + (n_out, dim), pt.float64, seeds.device, who, "paths")
+    length = _out_tensor(length, shape, pt.int32, seeds.device, who, "length")
+    status = _out_tensor(status, shape, pt.int32, seeds.device, who, "status")
+    cells = _out_tensor(cells, shape, pt.int32, seeds.device, who, "cells")
+    check(_lib.hip_lib().s3_trace(mode, _ptr(index.starts), _ptr(index.ends), _ptr(index.ids), n_cells, dim, index.depth,
+                                  C.c_void_p(index.origin.ctypes.data), index.h_min, _ptr(index.centers), _ptr(index.levels), index.width,
+                                  _ptr(faces), _ptr(velocity), DTYPE_CODE[velocity.dtype], t, dim * t, n_nodes, _ptr(seeds), n_seeds,
+                                  _ptr(order), int(n_steps), int(substeps), int(every), TRACE_STEP_RULES[rule], step, int(direction),
+                                  _ptr(paths), _ptr(length), _ptr(status), _ptr(cells), _stream()), "s3_trace")
+    return paths, length, status, cells
+
+
+def trace_stream(index, faces, velocity, seeds, n_steps, step="cell", cfl=0.5, dt=None, direction=1, every=1, order=None,
+                 paths=None, length=None, status=None, cells=None):
+    """streamlines of every column of a node velocity (s3_trace, S3_TRACE_STREAM).  ``index``: the ``CellIndex`` of the grid; ``faces``
+    int32 [n_cells, 2^dim]; ``velocity`` float32 / float64 [n_nodes, dim, T] contiguous; ``seeds`` float64 [n_seeds, dim]; all on the
+    device.  ``n_steps`` RK4 steps of ``step="cell"`` (``dt = cfl * h / |v|`` at every step) or ``step="time"`` (fixed ``dt``) in
+    ``direction`` 1 | -1; every ``every``-th accepted step is recorded.  ``order`` int32 [n_seeds]: the launch order of the seeds.
+    -> (paths f64 [n_seeds, T, 1 + n_steps // every, dim] with the seed in row 0 and NaN rows past the length, length, status
+    (``TRACE_STATUS``), cells (the cell of the last position): int32 [n_seeds, T]), written into the tensors given."""
+    if step == "time" and dt is None:
+        raise ValueError("trace_stream: step 'time' needs dt")
+    return _trace(0, "trace_stream", index, faces, velocity, seeds, order, n_steps, 1, every, step, dt if step == "time" else cfl,
+                  direction, paths, length, status, cells)
+
+
+def trace_path(index, faces, velocity, seeds, dt_snapshot, substeps=4, direction=1, order=None, paths=None, length=None, status=None,
+               cells=None):
+    """pathlines through the snapshots of a node velocity (s3_trace, S3_TRACE_PATH): arguments as ``trace_stream``; ``substeps`` RK4
+    steps of ``dt_snapshot / substeps`` per snapshot interval, the velocity blended linearly in time; ``direction`` -1 runs from the
+    last column to the first.  ``order``: launch the seeds in ``spatial_order``.  -> (paths f64 [n_seeds, T, dim]: the position at
+    every snapshot, the seed in column 0 (T - 1 backward), NaN past the length; length, status, cells: int32 [n_seeds])."""
+    dt_snapshot = float(dt_snapshot)
+    if not (np.isfinite(dt_snapshot) and dt_snapshot > 0.0) or int(substeps) < 1:
+        raise ValueError(f"trace_path: dt_snapshot must be positive and finite and substeps positive, got {dt_snapshot!r} and {substeps}")
+    return _trace(1, "trace_path", index, faces, velocity, seeds, order, 0, substeps, 1, "time", dt_snapshot / int(substeps), direction,
+                  paths, length, status, cells)
+
+
 ISO_COUNT_BYTES = 256 << 20         # the largest count array [T_b, n_cells] int32 of one isosurface launch
 ISO_MAX_PRIMITIVES = {2: 2, 3: 12}  # per cell and snapshot
 
