@@ -19,7 +19,7 @@ from os.path import abspath, dirname, join
 import torch as pt
 
 sys.path.insert(0, dirname(dirname(abspath(__file__))))
-from sparsespatialsampling_amd import Gradient, Probe, hipops, welch                    # noqa: E402
+from sparsespatialsampling_amd import Gradient, Grid, Probe, hipops, welch              # noqa: E402
 from sparsespatialsampling_amd.geometry import CubeGeometry, CylinderGeometry3D         # noqa: E402
 from sparsespatialsampling_amd.metrics import temporal_std                              # noqa: E402
 from sparsespatialsampling_amd.sampling import plane                                    # noqa: E402
@@ -68,7 +68,8 @@ if __name__ == "__main__":
     # a z-plane at mid-span, 600 x 500 pixels over the whole domain and a margin: every pixel gets the value of the cell that holds it
     shape = (600, 500)
     pixels = plane([-0.1, -0.1, 0.157], [2.6, 0.0, 0.0], [0.0, 2.2, 0.0], shape)
-    probe = Probe.from_s_cube(s_cube, pixels)
+    grid = Grid.from_s_cube(s_cube)                 # uploaded once, indexed once, for the plane and for the station below
+    probe = Probe.from_grid(grid, pixels)
     inside = probe.inside.reshape(shape)
     frames = hipops.snapshot_major(probe.sample(vort), 1, n_snapshots).view(n_snapshots, *shape)      # [T, 600, 500] on the device
     mean_frame = frames.mean(dim=0).cpu()
@@ -76,7 +77,7 @@ if __name__ == "__main__":
           f"time-mean vorticity magnitude on the plane: up to {float(mean_frame[pt.from_numpy(inside)].max()):.2f}")
 
     # the time series of v at a probe position in the wake, straight into welch
-    station = Probe.from_s_cube(s_cube, pt.tensor([[1.5, 1.07, 0.157]], dtype=pt.float64))
+    station = Probe.from_grid(grid, pt.tensor([[1.5, 1.07, 0.157]], dtype=pt.float64))
     series = station.sample(u_grid[:, 1, :].contiguous())                              # [1, T] float64, on the device
     freq, psd = welch(series, dt, nperseg=160)
     peak = int(psd[0, 1:].argmax()) + 1

@@ -22,7 +22,7 @@ import torch as pt
 sys.path.insert(0, dirname(dirname(abspath(__file__))))
 sys.path.insert(0, dirname(abspath(__file__)))
 from s3_for_synthetic_slice import velocity                                              # noqa: E402
-from sparsespatialsampling_amd import Gradient, Tracer, hipops                          # noqa: E402
+from sparsespatialsampling_amd import Gradient, Grid, Tracer, hipops                    # noqa: E402
 from sparsespatialsampling_amd.const import DATA                                        # noqa: E402
 from sparsespatialsampling_amd.data import Dataloader                                   # noqa: E402
 from sparsespatialsampling_amd.export import ExportData                                 # noqa: E402
@@ -66,7 +66,8 @@ if __name__ == "__main__":
     loader = Dataloader(save_path, "streamlines.h5")
     with open_h5(join(save_path, "streamlines.h5"), "r") as f:
         u_nodes = hipops.to_device(np.stack([f.read(f"{DATA}/{t}/u_vertices") for t in times], axis=-1))      # [N_nodes, 2, T] fp32
-    tracer = Tracer.from_dataloader(loader)
+    grid = Grid.from_dataloader(loader)             # uploaded once, indexed once: the tracer and every colouring below rest on it
+    tracer = Tracer.from_grid(grid)
 
     # streamlines of every snapshot from a line of seeds upstream, both ways, about half a cell per step
     seeds = line([0.3, 0.6], [0.3, 1.4], 41)

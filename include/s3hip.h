@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 16
+#define S3_ABI_VERSION 17
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -407,12 +407,21 @@ int s3_grad_apply(const double *d_coef /*[n,k,dim]*/, const int32_t *d_idx /*[n,
  *     origin = corner - ceil((corner - lo)/H - 1e-9) * H
  *     a      = rint(((c - h/2) - origin) / h_min)                  the anchor of a leaf: an integer vector, a multiple of 2^(L-l)
  *     key(i) = bit b of i[axis] at position b*dim + axis           the leaf owns the keys [key(a), key(a) + 2^(dim (L-l)))
+ * s3_grid describes such a grid once, for every entry point that looks something up in it (here and in the tracer below).  It is a
+ * plain description of memory the caller owns; nothing is allocated or kept by the library:
+ *     d_starts, d_ends, d_ids      the index: sorted range starts and ends (uint64 keys) and the cell of each range, n_cells entries each
+ *     dim, depth, origin, h_min    the lattice: dim 2 | 3, depth = L, origin[3] (the entries past dim are not read), h_min = h(L)
+ *     n_cells, d_centers, d_levels, width      the grid itself: centres [n_cells][dim] f64, levels [n_cells] int32, the initial cell size
+ *     d_faces                      [n_cells][2^dim] int32, the corner nodes of every cell; NULL where no node field is read
+ * An entry point that takes a grid requires: n_cells in [1, 2^31), dim 2 | 3, depth >= 0 and dim * depth <= 63, h_min > 0, width finite
+ * and positive and, when there is work, every array but d_faces non-null; d_faces non-null where the mode reads node fields.
+ *
  * s3_cell_index computes the keys on the device, sorts (key, cell) with s3_sort_pairs and checks that the sorted ranges are
- * disjoint.  It writes the sorted range starts, ends and cell ids (d_starts, d_ends, d_ids: n entries each) and the lattice
- * (h_origin[3], *h_hmin, *h_depth = L) and returns when they are complete.  A grid is REFUSED with S3_EINVAL, the counts in
- * h_refused[4]: [0] cells with an anchor more than 1e-6 lattice units off an integer or outside [0, 2^L), [1] cells whose anchor is
- * no multiple of 2^(L-l), [2] sorted ranges that reach into their successor, [3] dim * L where that exceeds 63.  2:1 balance is
- * not assumed.
+ * disjoint.  It writes the sorted range starts, ends and cell ids (d_starts, d_ends, d_ids: n entries each) and returns when they
+ * are complete; then *h_grid describes the grid: these three arrays, the lattice, n, d_centers, d_levels and width, d_faces NULL
+ * (the caller sets it).  A grid is REFUSED with S3_EINVAL, *h_grid untouched, the counts in h_refused[4]: [0] cells with an anchor
+ * more than 1e-6 lattice units off an integer or outside [0, 2^L), [1] cells whose anchor is no multiple of 2^(L-l), [2] sorted
+ * ranges that reach into their successor, [3] dim * L where that exceeds 63.  2:1 balance is not assumed.
  *
  * s3_cell_locate, one query per thread: i = floor((x - origin)/h_min) per axis (half-open: a point on a face belongs to the upper
  * cell), binary search of key(i) over the sorted starts, range test.  d_out[q] (int32, one entry per point, caller's cell
@@ -424,9 +433,9 @@ int s3_grad_apply(const double *d_coef /*[n,k,dim]*/, const int32_t *d_idx /*[n,
  * ELEMENTS (0 = n_comp * row_len), read where they lie; n_comp is 1, 2 or 3 per launch (a wider field goes in groups: offset d_field
  * and d_out, keep the pitches).  Row q of d_out (f64, pitch out_stride elements, 0 = n_comp * row_len) receives [n_comp][row_len]
  * for point q = d_rows[j] (d_rows NULL: q = j) with id = d_cell[q]:
- *     S3_SAMPLE_CELL    (double) field[id]: a bit-exact copy; n_field_rows = rows of the field (cells).  dim, d_points, d_centers,
- *                       d_levels, d_faces, n_cells and width are not read.
- *     S3_SAMPLE_LINEAR  the field lives on the grid NODES (n_field_rows of them), d_faces [n_cells][2^dim] lists the corners of a
+ *     S3_SAMPLE_CELL    (double) field[id]: a bit-exact copy; n_field_rows = rows of the field (cells).  grid and d_points are not
+ *                       read (NULL will do).
+ *     S3_SAMPLE_LINEAR  the field lives on the grid NODES (n_field_rows of them), grid->d_faces lists the corners of a
  *                       cell in the order (-,-), (-,+), (+,+), (+,-) in 2-D and that order at z+, then at z-, in 3-D:
  *                           xi_a = clamp((x_a - (c_a - h/2)) / h, 0, 1)                                    in f64, as written
  *                           w_m  = prod_a (s_ma > 0 ? xi_a : 1 - xi_a), evaluated as t = (s_m0 > 0 ? xi_0 : 1 - xi_0), then
@@ -437,21 +446,29 @@ int s3_grad_apply(const double *d_coef /*[n,k,dim]*/, const int32_t *d_idx /*[n,
  * No floating-point atomics: the same inputs give the same bits on every run, whatever row_len and n_comp. */
 #define S3_SAMPLE_CELL 0
 #define S3_SAMPLE_LINEAR 1
+typedef struct s3_grid {
+    const uint64_t *d_starts, *d_ends; /*[n_cells]*/
+    const int32_t *d_ids;              /*[n_cells]*/
+    int dim, depth;
+    double origin[3], h_min;
+    int64_t n_cells;
+    const double *d_centers;           /*[n_cells,dim]*/
+    const int32_t *d_levels;           /*[n_cells]*/
+    double width;
+    const int32_t *d_faces;            /*[n_cells,2^dim] or NULL*/
+} s3_grid;
 int s3_cell_index(const double *d_centers /*[n,dim]*/, const int32_t *d_levels /*[n]*/, int64_t n, int dim, double width,
-                  uint64_t *d_starts /*[n]*/, uint64_t *d_ends /*[n]*/, int32_t *d_ids /*[n]*/, double *h_origin /*[3]*/,
-                  double *h_hmin, int *h_depth, int64_t *h_refused /*[4]*/, s3_stream stream);
-int s3_cell_locate(const uint64_t *d_starts, const uint64_t *d_ends, const int32_t *d_ids, int64_t n_cells, int dim, int depth,
-                   const double *h_origin /*[3]*/, double h_min, const double *d_points /*[nq,dim]*/, int64_t nq,
-                   const int32_t *d_rows /*[nq] or NULL*/, int32_t *d_out /*[nq]*/, s3_stream stream);
+                  uint64_t *d_starts /*[n]*/, uint64_t *d_ends /*[n]*/, int32_t *d_ids /*[n]*/, s3_grid *h_grid,
+                  int64_t *h_refused /*[4]*/, s3_stream stream);
+int s3_cell_locate(const s3_grid *grid, const double *d_points /*[nq,dim]*/, int64_t nq, const int32_t *d_rows /*[nq] or NULL*/,
+                   int32_t *d_out /*[nq]*/, s3_stream stream);
 int s3_cell_sample(int mode, const int32_t *d_cell /*[nq]*/, int64_t nq, const int32_t *d_rows /*[nq] or NULL*/, const void *d_field,
-                   int dtype, int n_comp, int64_t row_len, int64_t in_stride, int64_t n_field_rows, int dim,
-                   const double *d_points /*[nq,dim]*/, const double *d_centers /*[n_cells,dim]*/, const int32_t *d_levels /*[n_cells]*/,
-                   double width, const int32_t *d_faces /*[n_cells,2^dim]*/, int64_t n_cells, double *d_out, int64_t out_stride,
-                   s3_stream stream);
+                   int dtype, int n_comp, int64_t row_len, int64_t in_stride, int64_t n_field_rows, const s3_grid *grid,
+                   const double *d_points /*[nq,dim]*/, double *d_out, int64_t out_stride, s3_stream stream);
 
 /* ---- streamlines and pathlines of node velocity fields (csrc/trace.hip; no counterpart in the reference) ----
- * The grid, its index and its lattice are those of s3_cell_index; the velocity lives on the grid NODES: d_field rows [dim][row_len] f32 or
- * f64 (dtype: S3_DTYPE_*) with pitch in_stride ELEMENTS (0 = dim * row_len), read where they lie, component c of node n at column t at
+ * The grid is the s3_grid of s3_cell_index with d_faces set (its fields are stated there); the velocity lives on the grid NODES:
+ * d_field rows [dim][row_len] f32 or f64 (dtype: S3_DTYPE_*) with pitch in_stride ELEMENTS (0 = dim * row_len), read where they lie, component c of node n at column t at
  * d_field[n * in_stride + c * row_len + t].  One lane per particle carries the whole loop.  This text is normative.
  *   velocity    at a position x in column t: the cell s3_cell_locate gives x (floored f64 lattice quotient, range test before the
  *               integer conversion, half-open cells, the upper cell on a face) and the S3_SAMPLE_LINEAR blend of its 2^dim corner rows
@@ -494,12 +511,10 @@ int s3_cell_sample(int mode, const int32_t *d_cell /*[nq]*/, int64_t nq, const i
 #define S3_TRACE_LEFT 1
 #define S3_TRACE_STAGNANT 2
 #define S3_TRACE_SEED_OUTSIDE 3
-int s3_trace(int mode, const uint64_t *d_starts, const uint64_t *d_ends, const int32_t *d_ids, int64_t n_cells, int dim, int depth,
-             const double *h_origin /*[3]*/, double h_min, const double *d_centers /*[n_cells,dim]*/, const int32_t *d_levels /*[n_cells]*/,
-             double width, const int32_t *d_faces /*[n_cells,2^dim]*/, const void *d_field, int dtype, int64_t row_len, int64_t in_stride,
-             int64_t n_nodes, const double *d_seeds /*[n_seeds,dim]*/, int64_t n_seeds, const int32_t *d_order /*[n_seeds] or NULL*/,
-             int64_t n_steps, int substeps, int every, int step_rule, double step /*dt or cfl, > 0*/, int direction /*1 | -1*/,
-             double *d_paths, int32_t *d_length, int32_t *d_status, int32_t *d_cell, s3_stream stream);
+int s3_trace(int mode, const s3_grid *grid, const void *d_field, int dtype, int64_t row_len, int64_t in_stride, int64_t n_nodes,
+             const double *d_seeds /*[n_seeds,dim]*/, int64_t n_seeds, const int32_t *d_order /*[n_seeds] or NULL*/, int64_t n_steps,
+             int substeps, int every, int step_rule, double step /*dt or cfl, > 0*/, int direction /*1 | -1*/, double *d_paths,
+             int32_t *d_length, int32_t *d_status, int32_t *d_cell, s3_stream stream);
 
 /* ---- isosurfaces (3-D) and contour lines (2-D) of node fields by marching simplices (csrc/iso.hip; no counterpart in the reference) ----
  * Inputs: d_nodes [n_nodes][dim] f64; d_faces [n_cells][2^dim] int32 in the corner order above ((-,-), (-,+), (+,+), (+,-) in 2-D;

@@ -20,7 +20,7 @@ if _os.environ.get("S3_KEEP_RUNTIME_PINNING") != "1":
 
 from .version import __version__
 
-__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "Probe", "Isosurface", "IsoResult", "Tracer", "Paths", "__version__"]
+__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "Grid", "Probe", "Isosurface", "IsoResult", "Tracer", "Paths", "__version__"]
 
 
 def __getattr__(name):
@@ -37,6 +37,9 @@ def __getattr__(name):
     if name == "Gradient":
         from . import differential
         return differential.Gradient
+    if name == "Grid":
+        from . import grid
+        return grid.Grid
     if name == "Probe":
         from . import sampling
         return sampling.Probe

@@ -26,10 +26,21 @@ class S3HipError(RuntimeError):
 
 _hip = None
 _topo = None
-ABI_VERSION = 16         # S3_ABI_VERSION of include/s3hip.h this file was written against
+ABI_VERSION = 17         # S3_ABI_VERSION of include/s3hip.h this file was written against
 _REBUILD = "python -c 'import __graft_entry__ as g; g.build()'"
 
 c_i64, c_i32, c_int, c_dbl, c_vp = C.c_int64, C.c_int32, C.c_int, C.c_double, C.c_void_p
+
+
+
+class S3Grid(C.Structure):
+    """``s3_grid`` of include/s3hip.h: a generated grid, its index and its lattice, described once for ``s3_cell_locate``,
+    ``s3_cell_sample`` and ``s3_trace``; ``s3_cell_index`` fills it"""
+    _fields_ = [("d_starts", c_vp), ("d_ends", c_vp), ("d_ids", c_vp), ("dim", c_int), ("depth", c_int), ("origin", c_dbl * 3),
+                ("h_min", c_dbl), ("n_cells", c_i64), ("d_centers", c_vp), ("d_levels", c_vp), ("width", c_dbl), ("d_faces", c_vp)]
+
+
+c_grid = C.POINTER(S3Grid)
 
 # name -> (restype, argtypes); must list every symbol include/s3hip.h declares (tests/test_abi.py checks this)
 HIP_SIGNATURES = {
@@ -86,12 +97,11 @@ HIP_SIGNATURES = {
                                c_vp, c_vp, c_vp]),
     "s3_grad_coeff": (c_int, [c_vp, c_i64, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, C.POINTER(c_i64), c_vp]),
     "s3_grad_apply": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_int, c_vp, c_i64, c_vp]),
-    "s3_cell_index": (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, C.POINTER(c_dbl), C.POINTER(c_int), c_vp, c_vp]),
-    "s3_cell_locate": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_dbl, c_vp, c_i64, c_vp, c_vp, c_vp]),
-    "s3_cell_sample": (c_int, [c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i64,
-                               c_vp, c_i64, c_vp]),
-    "s3_trace": (c_int, [c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_dbl, c_vp, c_vp, c_dbl, c_vp, c_vp, c_int, c_i64, c_i64, c_i64,
-                         c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "s3_cell_index": (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp, c_vp, c_grid, c_vp, c_vp]),
+    "s3_cell_locate": (c_int, [c_grid, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "s3_cell_sample": (c_int, [c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_grid, c_vp, c_vp, c_i64, c_vp]),
+    "s3_trace": (c_int, [c_int, c_grid, c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_dbl, c_int,
+                         c_vp, c_vp, c_vp, c_vp, c_vp]),
     "s3_iso_count": (c_int, [c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp]),
     "s3_iso_emit": (c_int, [c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "s3_interp": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_i64, c_i64, c_vp, c_vp]),

@@ -28,11 +28,24 @@ struct Lattice {
 
 __host__ __device__ inline double cell_size(double width, int level) { return width / (double)(1ull << level); }
 
-inline Lattice make_lattice(const double *h_origin, int dim, double h_min, int depth) {
+// what every entry point that takes an s3_grid requires of it (include/s3hip.h states it once); `work`: something is looked up, so
+// the arrays are read; `need_faces`: node fields are read through d_faces
+inline int check_grid(const char *who, const s3_grid *g, bool need_faces, bool work) {
+    S3_REQUIRE(g, "%s: null grid", who);
+    S3_REQUIRE(g->n_cells >= 1 && g->n_cells < ((int64_t)1 << 31) && (g->dim == 2 || g->dim == 3), "%s: bad grid n_cells=%lld dim=%d", who,
+               (long long)g->n_cells, g->dim);
+    S3_REQUIRE(g->depth >= 0 && g->dim * g->depth <= 63 && g->h_min > 0.0, "%s: bad lattice (depth %d, h_min %g)", who, g->depth, g->h_min);
+    S3_REQUIRE(g->width > 0.0 && std::isfinite(g->width), "%s: width %g is no cell size", who, g->width);
+    S3_REQUIRE(!work || (g->d_starts && g->d_ends && g->d_ids && g->d_centers && g->d_levels), "%s: null array in the grid", who);
+    S3_REQUIRE(!work || !need_faces || g->d_faces, "%s: the grid has no faces (d_faces) to read node fields through", who);
+    return S3_OK;
+}
+
+inline Lattice make_lattice(const s3_grid &g) {
     Lattice lat{};
-    for (int a = 0; a < dim; ++a) lat.origin[a] = h_origin[a];
-    lat.h_min = h_min;
-    lat.depth = depth;
+    for (int a = 0; a < g.dim; ++a) lat.origin[a] = g.origin[a];
+    lat.h_min = g.h_min;
+    lat.depth = g.depth;
     return lat;
 }
 

@@ -310,9 +310,8 @@ using namespace s3;
 extern "C" {
 
 int s3_cell_index(const double *d_centers, const int32_t *d_levels, int64_t n, int dim, double width, uint64_t *d_starts,
-                  uint64_t *d_ends, int32_t *d_ids, double *h_origin, double *h_hmin, int *h_depth, int64_t *h_refused,
-                  s3_stream stream) {
-    S3_REQUIRE(h_origin && h_hmin && h_depth && h_refused, "s3_cell_index: null output");
+                  uint64_t *d_ends, int32_t *d_ids, s3_grid *h_grid, int64_t *h_refused, s3_stream stream) {
+    S3_REQUIRE(h_grid && h_refused, "s3_cell_index: null output");
     for (int i = 0; i < 4; ++i) h_refused[i] = 0;
     S3_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && (dim == 2 || dim == 3), "s3_cell_index: bad shape n=%lld dim=%d", (long long)n, dim);
     S3_REQUIRE(width > 0.0 && std::isfinite(width), "s3_cell_index: width %g is no cell size", width);
@@ -371,34 +370,29 @@ int s3_cell_index(const double *d_centers, const int32_t *d_levels, int64_t n, i
     h_refused[2] = (int64_t)counts[2];
     S3_REQUIRE(counts[2] == 0, "s3_cell_index: %llu of %lld cells overlap their successor in Morton order", counts[2], (long long)n);
 
-    for (int a = 0; a < 3; ++a) h_origin[a] = lat.origin[a];
-    *h_hmin = lat.h_min;
-    *h_depth = lat.depth;
+    *h_grid = s3_grid{d_starts, d_ends, d_ids, dim, lat.depth, {lat.origin[0], lat.origin[1], lat.origin[2]}, lat.h_min, n, d_centers, d_levels,
+                      width, nullptr};
     return S3_OK;
 }
 
-int s3_cell_locate(const uint64_t *d_starts, const uint64_t *d_ends, const int32_t *d_ids, int64_t n_cells, int dim, int depth,
-                   const double *h_origin, double h_min, const double *d_points, int64_t nq, const int32_t *d_rows, int32_t *d_out,
-                   s3_stream stream) {
-    S3_REQUIRE(n_cells >= 1 && n_cells < ((int64_t)1 << 31) && nq >= 0 && nq < ((int64_t)1 << 31) && (dim == 2 || dim == 3),
-               "s3_cell_locate: bad shape n_cells=%lld nq=%lld dim=%d", (long long)n_cells, (long long)nq, dim);
-    S3_REQUIRE(depth >= 0 && dim * depth <= 63 && h_origin && h_min > 0.0, "s3_cell_locate: bad lattice (depth %d)", depth);
+int s3_cell_locate(const s3_grid *grid, const double *d_points, int64_t nq, const int32_t *d_rows, int32_t *d_out, s3_stream stream) {
+    S3_REQUIRE(nq >= 0 && nq < ((int64_t)1 << 31), "s3_cell_locate: bad shape nq=%lld", (long long)nq);
+    if (const int rc = check_grid("s3_cell_locate", grid, false, nq > 0)) return rc;
     if (nq == 0) return S3_OK;
-    S3_REQUIRE(d_starts && d_ends && d_ids && d_points && d_out, "s3_cell_locate: null array");
-    const Lattice lat = make_lattice(h_origin, dim, h_min, depth);
+    S3_REQUIRE(d_points && d_out, "s3_cell_locate: null array");
+    const Lattice lat = make_lattice(*grid);
     hipStream_t st = as_stream(stream);
-    if (dim == 2)
-        cell_locate_kernel<2><<<grid_for(nq, 256), 256, 0, st>>>(d_starts, d_ends, d_ids, n_cells, lat, d_points, nq, d_rows, d_out);
+    if (grid->dim == 2)
+        cell_locate_kernel<2><<<grid_for(nq, 256), 256, 0, st>>>(grid->d_starts, grid->d_ends, grid->d_ids, grid->n_cells, lat, d_points, nq, d_rows, d_out);
     else
-        cell_locate_kernel<3><<<grid_for(nq, 256), 256, 0, st>>>(d_starts, d_ends, d_ids, n_cells, lat, d_points, nq, d_rows, d_out);
+        cell_locate_kernel<3><<<grid_for(nq, 256), 256, 0, st>>>(grid->d_starts, grid->d_ends, grid->d_ids, grid->n_cells, lat, d_points, nq, d_rows, d_out);
     S3_LAUNCH_CHECK();
     return S3_OK;
 }
 
 int s3_cell_sample(int mode, const int32_t *d_cell, int64_t nq, const int32_t *d_rows, const void *d_field, int dtype, int n_comp,
-                   int64_t row_len, int64_t in_stride, int64_t n_field_rows, int dim, const double *d_points, const double *d_centers,
-                   const int32_t *d_levels, double width, const int32_t *d_faces, int64_t n_cells, double *d_out, int64_t out_stride,
-                   s3_stream stream) {
+                   int64_t row_len, int64_t in_stride, int64_t n_field_rows, const s3_grid *grid, const double *d_points, double *d_out,
+                   int64_t out_stride, s3_stream stream) {
     S3_REQUIRE(mode == S3_SAMPLE_CELL || mode == S3_SAMPLE_LINEAR, "s3_cell_sample: unknown mode %d", mode);
     S3_REQUIRE(nq >= 0 && nq < ((int64_t)1 << 31) && row_len >= 1 && n_field_rows >= 1 && n_field_rows < ((int64_t)1 << 31),
                "s3_cell_sample: bad shape nq=%lld row_len=%lld rows=%lld", (long long)nq, (long long)row_len, (long long)n_field_rows);
@@ -408,21 +402,21 @@ int s3_cell_sample(int mode, const int32_t *d_cell, int64_t nq, const int32_t *d
     if (out_stride <= 0) out_stride = n_comp * row_len;
     S3_REQUIRE(in_stride >= n_comp * row_len && out_stride >= n_comp * row_len, "s3_cell_sample: in_stride %lld / out_stride %lld shorter than a row",
                (long long)in_stride, (long long)out_stride);
-    if (mode == S3_SAMPLE_LINEAR) {
-        S3_REQUIRE(dim == 2 || dim == 3, "s3_cell_sample: dim=%d", dim);
-        S3_REQUIRE(n_cells >= 1 && n_cells < ((int64_t)1 << 31) && width > 0.0, "s3_cell_sample: bad grid n_cells=%lld width=%g", (long long)n_cells, width);
-    }
+    const bool linear = mode == S3_SAMPLE_LINEAR;
+    if (linear)
+        if (const int rc = check_grid("s3_cell_sample", grid, true, nq > 0)) return rc;
     if (nq == 0) return S3_OK;
-    S3_REQUIRE(d_cell && d_field && d_out, "s3_cell_sample: null array");
-    S3_REQUIRE(mode == S3_SAMPLE_CELL || (d_points && d_centers && d_levels && d_faces), "s3_cell_sample: linear mode needs points, centres, levels and faces");
-    const SampleArgs g{d_cell, nq, d_rows, d_field, n_field_rows, row_len, in_stride, d_points, d_centers, d_levels, d_faces, n_cells, width,
-                       d_out, out_stride, as_stream(stream)};
+    S3_REQUIRE(d_cell && d_field && d_out && (!linear || d_points), "s3_cell_sample: null array%s", linear ? " (linear mode needs the points)" : "");
+    const s3_grid none{};                                                       // S3_SAMPLE_CELL reads no grid
+    const s3_grid &gr = linear ? *grid : none;
+    const SampleArgs g{d_cell, nq, d_rows, d_field, n_field_rows, row_len, in_stride, d_points, gr.d_centers, gr.d_levels, gr.d_faces, gr.n_cells,
+                       gr.width, d_out, out_stride, as_stream(stream)};
     // the width of a lane's piece: every component row of every field row must start on a 16-byte boundary
     return dispatch_rows<WidestRowWidth>(dtype, row_width<WidestRowWidth>(dtype, d_field, row_len, in_stride), [&](auto row) {
         using T = typename decltype(row)::type;
         constexpr int VEC = decltype(row)::vec;
         if (mode == S3_SAMPLE_CELL) return sample_by_comp<T, VEC, 0>(g, n_comp);
-        return dim == 2 ? sample_by_comp<T, VEC, 2>(g, n_comp) : sample_by_comp<T, VEC, 3>(g, n_comp);
+        return gr.dim == 2 ? sample_by_comp<T, VEC, 2>(g, n_comp) : sample_by_comp<T, VEC, 3>(g, n_comp);
     });
 }
 

@@ -283,16 +283,13 @@ using namespace s3;
 
 extern "C" {
 
-int s3_trace(int mode, const uint64_t *d_starts, const uint64_t *d_ends, const int32_t *d_ids, int64_t n_cells, int dim, int depth,
-             const double *h_origin, double h_min, const double *d_centers, const int32_t *d_levels, double width, const int32_t *d_faces,
-             const void *d_field, int dtype, int64_t row_len, int64_t in_stride, int64_t n_nodes, const double *d_seeds, int64_t n_seeds,
-             const int32_t *d_order, int64_t n_steps, int substeps, int every, int step_rule, double step, int direction, double *d_paths,
-             int32_t *d_length, int32_t *d_status, int32_t *d_cell, s3_stream stream) {
+int s3_trace(int mode, const s3_grid *grid, const void *d_field, int dtype, int64_t row_len, int64_t in_stride, int64_t n_nodes,
+             const double *d_seeds, int64_t n_seeds, const int32_t *d_order, int64_t n_steps, int substeps, int every, int step_rule,
+             double step, int direction, double *d_paths, int32_t *d_length, int32_t *d_status, int32_t *d_cell, s3_stream stream) {
     S3_REQUIRE(mode == S3_TRACE_STREAM || mode == S3_TRACE_PATH, "s3_trace: unknown mode %d", mode);
     const bool path = mode == S3_TRACE_PATH;
-    S3_REQUIRE(n_cells >= 1 && n_cells < ((int64_t)1 << 31) && (dim == 2 || dim == 3), "s3_trace: bad grid n_cells=%lld dim=%d", (long long)n_cells, dim);
-    S3_REQUIRE(depth >= 0 && dim * depth <= 63 && h_origin && h_min > 0.0, "s3_trace: bad lattice (depth %d)", depth);
-    S3_REQUIRE(width > 0.0 && std::isfinite(width), "s3_trace: width %g is no cell size", width);
+    if (const int rc = check_grid("s3_trace", grid, true, n_seeds != 0)) return rc;
+    const int dim = grid->dim;
     S3_REQUIRE(dtype == S3_DTYPE_F32 || dtype == S3_DTYPE_F64, "s3_trace: unknown dtype %d", dtype);
     S3_REQUIRE(row_len >= (path ? 2 : 1) && n_nodes >= 1 && n_nodes < ((int64_t)1 << 31), "s3_trace: bad field row_len=%lld n_nodes=%lld%s",
                (long long)row_len, (long long)n_nodes, path ? " (a pathline needs two snapshots)" : "");
@@ -313,10 +310,10 @@ int s3_trace(int mode, const uint64_t *d_starts, const uint64_t *d_ends, const i
     }
     const int64_t n_out = path ? row_len : 1 + n_steps / every;
     if (n_seeds == 0) return S3_OK;
-    S3_REQUIRE(d_starts && d_ends && d_ids && d_centers && d_levels && d_faces && d_field && d_seeds, "s3_trace: null input array");
+    S3_REQUIRE(d_field && d_seeds, "s3_trace: null input array");
     S3_REQUIRE(d_paths && d_length && d_status && d_cell, "s3_trace: null output array");
-    const TraceArgs g{d_starts, d_ends, d_ids, n_cells, make_lattice(h_origin, dim, h_min, depth), d_centers, d_levels, width, d_faces,
-                      d_field, row_len, in_stride, n_nodes, d_seeds, n_seeds, d_order, n_steps, every, step_rule == S3_TRACE_STEP_CELL,
+    const TraceArgs g{grid->d_starts, grid->d_ends, grid->d_ids, grid->n_cells, make_lattice(*grid), grid->d_centers, grid->d_levels, grid->width,
+                      grid->d_faces, d_field, row_len, in_stride, n_nodes, d_seeds, n_seeds, d_order, n_steps, every, step_rule == S3_TRACE_STEP_CELL,
                       step, direction, n_out, d_paths, d_length, d_status, d_cell};
     hipStream_t st = as_stream(stream);
     return dtype == S3_DTYPE_F32 ? trace_by_shape<float>(g, dim, path, st) : trace_by_shape<double>(g, dim, path, st);

@@ -70,6 +70,7 @@ class Dataloader:
     faces = property(lambda self: self._array("faces"))
     levels = property(lambda self: self._array("levels"))
     metric = property(lambda self: self._array("metric"))
+    size_initial_cell = property(lambda self: self._size_initial_cell, doc="the edge of the initial cell, as the file states it")
 
     @property
     def write_times(self) -> List[str]:

@@ -364,10 +364,35 @@ class CellIndex:
     ``depth``) and the grid itself (``centers`` f64 [n, dim], ``levels`` int32 [n], ``width``), all arrays on the device"""
 
     def __init__(self, centers, levels, width, starts, ends, ids, origin, h_min, depth):
+        for t in (centers, levels, starts, ends, ids):
+            _ptr(t)                                 # (device-resident and contiguous: checked here once, not in every launch)
         self.centers, self.levels, self.width = centers, levels, float(width)
         self.starts, self.ends, self.ids = starts, ends, ids
         self.origin, self.h_min, self.depth = origin, float(h_min), int(depth)
         self.n_cells, self.dim = int(centers.shape[0]), int(centers.shape[1])
+        self._origin = (C.c_double * 3)(*origin)
+
+    def s3_grid(self, faces=None):
+        """the ``s3_grid`` of one call (``faces``: checked by the caller, ``_grid_faces``): nothing is kept of it, the tensors here and
+        ``faces`` own the memory it points to.  Plain ``data_ptr()`` reads: a launch-bound caller pays for every microsecond here."""
+        return _lib.S3Grid(self.starts.data_ptr(), self.ends.data_ptr(), self.ids.data_ptr(), self.dim, self.depth, self._origin, self.h_min,
+                           self.n_cells, self.centers.data_ptr(), self.levels.data_ptr(), self.width, None if faces is None else faces.data_ptr())
+
+
+def _cell_index(index, who):
+    if not isinstance(index, CellIndex):
+        raise TypeError(f"{who}: index must be what cell_index returned")
+    return index
+
+
+def _grid_faces(faces, who, index=None):
+    """-> (n_cells, dim) of ``faces`` as the kernels index them: contiguous int32 [n_cells, 2^dim] on the device, the cells and the
+    dimension those of ``index`` where one is given"""
+    shape = f"[{index.n_cells}, {1 << index.dim}]" if index is not None else "[n_cells, 4 | 8]"
+    if not (isinstance(faces, pt.Tensor) and faces.is_cuda and faces.dtype == pt.int32 and faces.is_contiguous() and faces.dim() == 2
+            and (int(faces.shape[1]) in (4, 8) if index is None else tuple(faces.shape) == (index.n_cells, 1 << index.dim))):
+        raise TypeError(f"{who}: faces must be a contiguous int32 device tensor {shape}")
+    return int(faces.shape[0]), 2 if int(faces.shape[1]) == 4 else 3
 
 
 def cell_index(centers, levels, width):
@@ -390,16 +415,15 @@ def cell_index(centers, levels, width):
     levels = levels.reshape(n).to(pt.int32).contiguous()
     starts = pt.empty(n, dtype=pt.int64, device=centers.device)
     ends, ids = pt.empty_like(starts), pt.empty(n, dtype=pt.int32, device=centers.device)
-    origin, refused = np.zeros(3, dtype=np.float64), np.zeros(4, dtype=np.int64)
-    h_min, depth = C.c_double(0.0), C.c_int(0)
+    grid, refused = _lib.S3Grid(), np.zeros(4, dtype=np.int64)
     lib = _lib.hip_lib()
-    rc = lib.s3_cell_index(_ptr(centers), _ptr(levels), n, dim, width, _ptr(starts), _ptr(ends), _ptr(ids), C.c_void_p(origin.ctypes.data),
-                           C.byref(h_min), C.byref(depth), C.c_void_p(refused.ctypes.data), _stream())
+    rc = lib.s3_cell_index(_ptr(centers), _ptr(levels), n, dim, width, _ptr(starts), _ptr(ends), _ptr(ids), C.byref(grid),
+                           C.c_void_p(refused.ctypes.data), _stream())
     if rc == -1 and refused.any():
         raise ValueError(f"cell_index: the grid of {n} cells is refused: " + lib.s3_last_error().decode(errors="replace")
                          + f" (off the lattice {refused[0]}, misaligned {refused[1]}, overlapping {refused[2]}, key bits {refused[3]})")
     check(rc, "s3_cell_index")
-    return CellIndex(centers, levels, width, starts, ends, ids, origin, h_min.value, depth.value)
+    return CellIndex(centers, levels, width, starts, ends, ids, np.array(grid.origin, dtype=np.float64), grid.h_min, grid.depth)
 
 
 def _query_points(points, dim, who):
@@ -413,14 +437,10 @@ def cell_locate(index, points, rows=None, out=None):
     """the cell that holds each point (s3_cell_locate): ``points`` float64 [nq, dim] on the device -> int32 [nq] in the caller's
     cell numbering, -1 where no cell holds the point (outside the domain, inside a body, NaN / infinite coordinates).  A point on
     a face belongs to the upper cell.  ``rows`` int32 [nq]: the order in which the points are launched (``spatial_order``)."""
-    if not isinstance(index, CellIndex):
-        raise TypeError("cell_locate: index must be what cell_index returned")
-    nq = _query_points(points, index.dim, "cell_locate")
+    nq = _query_points(points, _cell_index(index, "cell_locate").dim, "cell_locate")
     _launch_rows(rows, nq, "cell_locate")
     out = _out_tensor(out, (nq,), pt.int32, points.device, "cell_locate")
-    check(_lib.hip_lib().s3_cell_locate(_ptr(index.starts), _ptr(index.ends), _ptr(index.ids), index.n_cells, index.dim, index.depth,
-                                        C.c_void_p(index.origin.ctypes.data), index.h_min, _ptr(points), nq, _ptr(rows), _ptr(out),
-                                        _stream()), "s3_cell_locate")
+    check(_lib.hip_lib().s3_cell_locate(C.byref(index.s3_grid()), _ptr(points), nq, _ptr(rows), _ptr(out), _stream()), "s3_cell_locate")
     return out
 
 
@@ -446,26 +466,22 @@ def cell_sample(ids, field, mode="cell", rows=None, out=None, index=None, points
     if t < 1 or n_comp < 1 or n_rows < 1:
         raise ValueError(f"cell_sample: empty field {tuple(field.shape)}")
     _launch_rows(rows, nq, "cell_sample")
-    dim, n_cells, width, centers, levels = 0, 0, 0.0, None, None
+    grid = None
     if mode == "linear":
         if index is None or points is None or faces is None:
             raise ValueError("cell_sample: mode 'linear' needs index, points and faces")
-        if not isinstance(index, CellIndex):
-            raise TypeError("cell_sample: index must be what cell_index returned")
-        dim, n_cells, width, centers, levels = index.dim, index.n_cells, index.width, index.centers, index.levels
-        if _query_points(points, dim, "cell_sample") != nq:
+        if _query_points(points, _cell_index(index, "cell_sample").dim, "cell_sample") != nq:
             raise ValueError(f"cell_sample: {int(points.shape[0])} points for {nq} ids")
-        if not (isinstance(faces, pt.Tensor) and faces.is_cuda and faces.dtype == pt.int32 and faces.is_contiguous()
-                and tuple(faces.shape) == (n_cells, 1 << dim)):
-            raise TypeError(f"cell_sample: faces must be a contiguous int32 device tensor [{n_cells}, {1 << dim}]")
+        _grid_faces(faces, "cell_sample", index)
+        grid = C.byref(index.s3_grid(faces))
     else:
-        points = faces = None
+        points = None
     out = _out_tensor(out, (nq, n_comp, t), pt.float64, field.device, "cell_sample")
     lib, item = _lib.hip_lib(), field.element_size()
     for c0, group in _component_groups(n_comp):
         check(lib.s3_cell_sample(SAMPLE_MODES[mode], _ptr(ids), nq, _ptr(rows), C.c_void_p(field.data_ptr() + c0 * t * item),
-                                 DTYPE_CODE[field.dtype], group, t, in_stride, n_rows, dim, _ptr(points), _ptr(centers), _ptr(levels), width,
-                                 _ptr(faces), n_cells, C.c_void_p(out.data_ptr() + c0 * t * 8), n_comp * t, _stream()), "s3_cell_sample")
+                                 DTYPE_CODE[field.dtype], group, t, in_stride, n_rows, grid, _ptr(points),
+                                 C.c_void_p(out.data_ptr() + c0 * t * 8), n_comp * t, _stream()), "s3_cell_sample")
     return out
 
 
@@ -474,12 +490,8 @@ TRACE_STATUS = {"DONE": 0, "LEFT": 1, "STAGNANT": 2, "SEED_OUTSIDE": 3}         
 
 
 def _trace(mode, who, index, faces, velocity, seeds, order, n_steps, substeps, every, rule, step, direction, paths, length, status, cells):
-    if not isinstance(index, CellIndex):
-        raise TypeError(f"{who}: index must be what cell_index returned")
-    dim, n_cells = index.dim, index.n_cells
-    if not (isinstance(faces, pt.Tensor) and faces.is_cuda and faces.dtype == pt.int32 and faces.is_contiguous()
-            and tuple(faces.shape) == (n_cells, 1 << dim)):
-        raise TypeError(f"{who}: faces must be a contiguous int32 device tensor [{n_cells}, {1 << dim}]")
+    dim = _cell_index(index, who).dim
+    _grid_faces(faces, who, index)
     if not (isinstance(velocity, pt.Tensor) and velocity.is_cuda and velocity.dtype in DTYPE_CODE and velocity.dim() == 3
             and velocity.is_contiguous()):
         raise TypeError(f"{who}: velocity must be a contiguous float32 / float64 device tensor [n_nodes, {dim}, T]")
@@ -511,10 +523,8 @@ def _trace(mode, who, index, faces, velocity, seeds, order, n_steps, substeps, e
     length = _out_tensor(length, shape, pt.int32, seeds.device, who, "length")
     status = _out_tensor(status, shape, pt.int32, seeds.device, who, "status")
     cells = _out_tensor(cells, shape, pt.int32, seeds.device, who, "cells")
-    check(_lib.hip_lib().s3_trace(mode, _ptr(index.starts), _ptr(index.ends), _ptr(index.ids), n_cells, dim, index.depth,
-                                  C.c_void_p(index.origin.ctypes.data), index.h_min, _ptr(index.centers), _ptr(index.levels), index.width,
-                                  _ptr(faces), _ptr(velocity), DTYPE_CODE[velocity.dtype], t, dim * t, n_nodes, _ptr(seeds), n_seeds,
-                                  _ptr(order), int(n_steps), int(substeps), int(every), TRACE_STEP_RULES[rule], step, int(direction),
+    check(_lib.hip_lib().s3_trace(mode, C.byref(index.s3_grid(faces)), _ptr(velocity), DTYPE_CODE[velocity.dtype], t, dim * t, n_nodes, _ptr(seeds),
+                                  n_seeds, _ptr(order), int(n_steps), int(substeps), int(every), TRACE_STEP_RULES[rule], step, int(direction),
                                   _ptr(paths), _ptr(length), _ptr(status), _ptr(cells), _stream()), "s3_trace")
     return paths, length, status, cells
 
@@ -559,13 +569,11 @@ def _iso_inputs(field, faces, level, who):
     _, t, in_stride = _field_rows(field, who, 2)
     if t < 1 or int(field.shape[0]) < 1:
         raise ValueError(f"{who}: empty field {tuple(field.shape)}")
-    if not (isinstance(faces, pt.Tensor) and faces.is_cuda and faces.dtype == pt.int32 and faces.is_contiguous() and faces.dim() == 2
-            and int(faces.shape[1]) in (4, 8)):
-        raise TypeError(f"{who}: faces must be a contiguous int32 device tensor [n_cells, 4 | 8]")
+    n_cells, dim = _grid_faces(faces, who)
     level = float(level)
     if not np.isfinite(level):
         raise ValueError(f"{who}: the level must be finite, got {level!r}")
-    return field, t, in_stride, int(faces.shape[0]), 2 if int(faces.shape[1]) == 4 else 3, level
+    return field, t, in_stride, n_cells, dim, level
 
 
 def iso_count(field, faces, level, out=None):

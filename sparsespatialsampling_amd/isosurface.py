@@ -19,6 +19,7 @@ import torch as pt
 
 from . import hipops
 from .arrays import Side, as_tensor, resident
+from .grid import Grid
 
 
 class IsoResult:
@@ -99,36 +100,36 @@ class IsoResult:
 
 class Isosurface:
     """``nodes`` [N_nodes, d] and ``faces`` [N_cells, 2^d] (the corner nodes of every cell) of a generated grid, d = 2 | 3; numpy or
-    torch, host or device.  ``extract`` and ``count`` take node fields [N_nodes] or [N_nodes, T], float32 or float64, numpy or torch,
+    torch, host or device: the corner part of a ``grid.Grid``, kept as ``grid``; ``from_grid`` takes one that is there already.
+    ``extract`` and ``count`` take node fields [N_nodes] or [N_nodes, T], float32 or float64, numpy or torch,
     host or device; a window ``field[:, t0:t1]`` of a field that lives on the device is read where it lies (``arrays.resident``).
     Results come back on the side (and as the kind of array) the field came from."""
 
     def __init__(self, nodes, faces):
-        nodes, faces = as_tensor(nodes, "nodes"), as_tensor(faces, "faces")
-        if nodes.dim() != 2 or int(nodes.shape[1]) not in (2, 3):
-            raise ValueError(f"expected nodes [Nn, 2 | 3], got {tuple(nodes.shape)}")
-        self.n_nodes, self.dim = int(nodes.shape[0]), int(nodes.shape[1])
-        if faces.dim() != 2 or int(faces.shape[1]) != 1 << self.dim or faces.is_floating_point():
-            raise ValueError(f"expected integer faces [Nc, {1 << self.dim}], got {tuple(faces.shape)} {faces.dtype}")
-        self.n_cells = int(faces.shape[0])
-        if self.n_nodes < 1:
-            raise ValueError("a grid without nodes")
-        if self.n_cells and (int(faces.min()) < 0 or int(faces.max()) >= self.n_nodes):
-            raise ValueError(f"faces name nodes outside [0, {self.n_nodes})")
-        self._nodes = hipops.to_device(nodes, pt.float64)
-        self._faces = hipops.to_device(faces, pt.int32)
+        self._on(Grid(nodes=nodes, faces=faces))
+
+    def _on(self, grid):
+        if grid.faces is None:
+            raise ValueError("an isosurface cuts fields on the grid's nodes: build the Grid with nodes and faces")
+        self.grid, self.dim, self.n_cells, self.n_nodes = grid, grid.dim, grid.n_cells, grid.n_nodes
+        self._nodes, self._faces = grid.nodes, grid.faces
+
+    @classmethod
+    def from_grid(cls, grid):
+        """a ``grid.Grid`` with its corner part (the cell part is not needed), which is not uploaded again"""
+        self = cls.__new__(cls)
+        self._on(grid)
+        return self
 
     @classmethod
     def from_dataloader(cls, loader):
         """the grid of an S^3 file (``data.Dataloader``)"""
-        return cls(loader.nodes, loader.faces)
+        return cls.from_grid(Grid.from_dataloader(loader))
 
     @classmethod
     def from_s_cube(cls, s_cube):
         """the grid of a ``SparseSpatialSampling`` after ``execute_grid_generation``"""
-        if getattr(s_cube, "centers", None) is None:
-            raise ValueError("the grid has not been generated yet: call execute_grid_generation() first")
-        return cls(s_cube.vertices, s_cube.faces)
+        return cls.from_grid(Grid.from_s_cube(s_cube))
 
     def _field(self, field, level):
         field, side = as_tensor(field, "field"), Side(field)

@@ -23,6 +23,7 @@ import torch as pt
 
 from . import hipops
 from .arrays import Side, as_tensor, resident
+from .grid import Grid
 
 
 # ---- point sets (host only) -------------------------------------------------------------------------------------------------
@@ -73,9 +74,9 @@ def raster(lo, hi, shape):
 # ---- the probe ---------------------------------------------------------------------------------------------------------------
 class Probe:
     """``points`` [Nq, d] located once in the grid (``centers`` [Nc, d], ``levels`` [Nc] or [Nc, 1], ``width``: the size of the
-    initial cell; numpy or torch, host or device).  ``nodes`` [Nn, d] and ``faces`` [Nc, 2^d] (the corner nodes of every cell) are
-    needed for ``mode="linear"`` only.  The grid is refused with ``ValueError`` when its cells are no disjoint dyadic boxes on one
-    lattice.
+    initial cell; numpy or torch, host or device: a ``grid.Grid``, kept as ``grid``; ``from_grid`` takes one that is there already).
+    ``nodes`` [Nn, d] and ``faces`` [Nc, 2^d] (the corner nodes of every cell) are needed for ``mode="linear"`` only.  The grid is
+    refused with ``ValueError`` when its cells are no disjoint dyadic boxes on one lattice.
 
     ``cell_ids`` (int32 [Nq], -1: no cell) and ``inside`` (bool [Nq]) come back in the caller's order, on the side (and as the kind
     of array) the points came from.  ``sample`` takes fields [rows, (n_comp,) T] (``[rows]``: one snapshot; rows = cells for
@@ -84,31 +85,16 @@ class Probe:
     the side the field came from, NaN where ``inside`` is False."""
 
     def __init__(self, centers, levels, width, points, nodes=None, faces=None):
+        self._locate(Grid(centers, levels, width, nodes, faces), points)
+
+    def _locate(self, grid, points):
         points, self._side = as_tensor(points, "points"), Side(points)
-        centers, levels = as_tensor(centers, "centers"), as_tensor(levels, "levels")
-        if centers.dim() != 2 or int(centers.shape[1]) not in (2, 3):
-            raise ValueError(f"expected centers [Nc, 2 | 3], got {tuple(centers.shape)}")
-        self.n_cells, self.dim = int(centers.shape[0]), int(centers.shape[1])
+        self.grid, self.dim, self.n_cells, self.n_nodes = grid, grid.dim, grid.n_cells, grid.n_nodes
         if points.dim() != 2 or int(points.shape[1]) != self.dim:
             raise ValueError(f"expected points [Nq, {self.dim}], got {tuple(points.shape)}")
-        if levels.numel() != self.n_cells or levels.is_floating_point():
-            raise ValueError(f"expected one integer level per cell ({self.n_cells}), got {tuple(levels.shape)} {levels.dtype}")
-        if (nodes is None) != (faces is None):
-            raise ValueError("nodes and faces go together")
         self.n_points = int(points.shape[0])
-        self._index = hipops.cell_index(hipops.to_device(centers, pt.float64), hipops.to_device(levels.reshape(-1), pt.int32), width)
+        self._index = grid.index
         self._points = hipops.to_device(points, pt.float64)
-        self._faces, self.n_nodes = None, None
-        if faces is not None:
-            faces, nodes = as_tensor(faces, "faces"), as_tensor(nodes, "nodes")
-            if tuple(faces.shape) != (self.n_cells, 1 << self.dim) or faces.is_floating_point():
-                raise ValueError(f"expected integer faces [{self.n_cells}, {1 << self.dim}], got {tuple(faces.shape)} {faces.dtype}")
-            if nodes.dim() != 2 or int(nodes.shape[1]) != self.dim:
-                raise ValueError(f"expected nodes [Nn, {self.dim}], got {tuple(nodes.shape)}")
-            self.n_nodes = int(nodes.shape[0])
-            if int(faces.min()) < 0 or int(faces.max()) >= self.n_nodes:
-                raise ValueError(f"faces name nodes outside [0, {self.n_nodes})")
-            self._faces = hipops.to_device(faces, pt.int32)
         if self.n_points:
             # the points are launched in Hilbert order: neighbouring slots then read the same few field rows
             self._rows = hipops.spatial_order(self._points)
@@ -117,17 +103,21 @@ class Probe:
             self._rows, self._ids = None, pt.empty(0, dtype=pt.int32, device=self._points.device)
 
     @classmethod
+    def from_grid(cls, grid, points):
+        """``points`` located in a ``grid.Grid``, which is neither uploaded nor indexed again"""
+        self = cls.__new__(cls)
+        self._locate(grid, points)
+        return self
+
+    @classmethod
     def from_dataloader(cls, loader, points):
-        """the grid of an S^3 file (``data.Dataloader``): centres, levels, the size of the initial cell and, for ``mode="linear"``,
-        the corner nodes and faces"""
-        return cls(loader.vertices, loader.levels, loader._size_initial_cell, points, nodes=loader.nodes, faces=loader.faces)
+        """the grid of an S^3 file (``data.Dataloader``)"""
+        return cls.from_grid(Grid.from_dataloader(loader), points)
 
     @classmethod
     def from_s_cube(cls, s_cube, points):
         """the grid of a ``SparseSpatialSampling`` after ``execute_grid_generation``"""
-        if getattr(s_cube, "centers", None) is None:
-            raise ValueError("the grid has not been generated yet: call execute_grid_generation() first")
-        return cls(s_cube.centers, s_cube.levels, float(s_cube.size_initial_cell), points, nodes=s_cube.vertices, faces=s_cube.faces)
+        return cls.from_grid(Grid.from_s_cube(s_cube), points)
 
     @property
     def cell_ids(self):
@@ -141,7 +131,7 @@ class Probe:
         """[rows, (n_comp,) T] -> float64 [Nq, (n_comp,) T]"""
         if mode not in hipops.SAMPLE_MODES:
             raise ValueError(f"unknown mode {mode!r}, expected one of {sorted(hipops.SAMPLE_MODES)}")
-        if mode == "linear" and self._faces is None:
+        if mode == "linear" and self.grid.faces is None:
             raise ValueError("mode 'linear' blends the corner values of a cell: build the Probe with nodes and faces")
         field, side = as_tensor(field, "field"), Side(field)
         shape = tuple(int(v) for v in field.shape)
@@ -152,7 +142,7 @@ class Probe:
             raise ValueError(f"{mode}: empty field {shape}")
         dev_field = resident(field)
         if self.n_points:
-            res = hipops.cell_sample(self._ids, dev_field, mode, rows=self._rows, index=self._index, points=self._points, faces=self._faces)
+            res = hipops.cell_sample(self._ids, dev_field, mode, rows=self._rows, index=self._index, points=self._points, faces=self.grid.faces)
         else:
             res = pt.empty((0,) + shape[1:], dtype=pt.float64, device=dev_field.device)
         return side.back(res.view((self.n_points,) + shape[1:]))

@@ -26,6 +26,7 @@ import torch as pt
 
 from . import hipops
 from .arrays import Side, as_tensor, resident
+from .grid import Grid
 from .sampling import Probe
 
 STATUS = hipops.TRACE_STATUS        # name -> code of ``Paths.status``
@@ -49,51 +50,45 @@ class Paths:
     def sample(self, field, mode="linear"):
         """another field of the grid at the recorded positions (``Probe``): [rows, (n_comp,) T_f] -> float64
         ``points.shape[:-1] + field.shape[1:]`` on the side of the field; NaN rows of a path stay NaN"""
-        t = self._tracer
-        flat = self.points.reshape(-1, t.dim)
-        probe = Probe(t._index.centers, t._index.levels, t._index.width, flat, nodes=t._nodes, faces=t._faces)
-        res = probe.sample(field, mode)
+        grid = self._tracer.grid
+        res = Probe.from_grid(grid, self.points.reshape(-1, grid.dim)).sample(field, mode)
         return res.reshape(tuple(self.points.shape[:-1]) + tuple(res.shape[1:]))
 
 
 class Tracer:
     """the grid (``centers`` [Nc, d], ``levels`` [Nc] or [Nc, 1], ``width``: the size of the initial cell, ``nodes`` [Nn, d] and
-    ``faces`` [Nc, 2^d]: the corner nodes of every cell; numpy or torch, host or device), indexed once (``hipops.cell_index``; a grid
-    whose cells are no disjoint dyadic boxes on one lattice is refused with ``ValueError``).
+    ``faces`` [Nc, 2^d]: the corner nodes of every cell; numpy or torch, host or device: a ``grid.Grid``, kept as ``grid``; ``from_grid``
+    takes one that is there already), indexed once (``hipops.cell_index``; a grid whose cells are no disjoint dyadic boxes on one
+    lattice is refused with ``ValueError``).
 
     ``velocity`` is [Nn, d, T] or [Nn, d] (one snapshot), float32 or float64, numpy or torch; on the device and contiguous it is read
     where it lies (``arrays.resident``).  ``seeds`` [n_seeds, d]; the results come back on their side."""
 
     def __init__(self, centers, levels, width, nodes, faces):
-        centers, levels = as_tensor(centers, "centers"), as_tensor(levels, "levels")
-        nodes, faces = as_tensor(nodes, "nodes"), as_tensor(faces, "faces")
-        if centers.dim() != 2 or int(centers.shape[1]) not in (2, 3):
-            raise ValueError(f"expected centers [Nc, 2 | 3], got {tuple(centers.shape)}")
-        self.n_cells, self.dim = int(centers.shape[0]), int(centers.shape[1])
-        if levels.numel() != self.n_cells or levels.is_floating_point():
-            raise ValueError(f"expected one integer level per cell ({self.n_cells}), got {tuple(levels.shape)} {levels.dtype}")
-        if tuple(faces.shape) != (self.n_cells, 1 << self.dim) or faces.is_floating_point():
-            raise ValueError(f"expected integer faces [{self.n_cells}, {1 << self.dim}], got {tuple(faces.shape)} {faces.dtype}")
-        if nodes.dim() != 2 or int(nodes.shape[1]) != self.dim:
-            raise ValueError(f"expected nodes [Nn, {self.dim}], got {tuple(nodes.shape)}")
-        self.n_nodes = int(nodes.shape[0])
-        if int(faces.min()) < 0 or int(faces.max()) >= self.n_nodes:
-            raise ValueError(f"faces name nodes outside [0, {self.n_nodes})")
-        self._index = hipops.cell_index(hipops.to_device(centers, pt.float64), hipops.to_device(levels.reshape(-1), pt.int32), width)
-        self._faces = hipops.to_device(faces, pt.int32)
-        self._nodes = hipops.to_device(nodes, pt.float64)
+        self._on(Grid(centers, levels, width, nodes, faces))
+
+    def _on(self, grid):
+        if grid.faces is None:
+            raise ValueError("a velocity lives on the grid's nodes: build the Grid with nodes and faces")
+        self.grid, self.dim, self.n_cells, self.n_nodes = grid, grid.dim, grid.n_cells, grid.n_nodes
+        self._index, self._faces = grid.index, grid.faces
+
+    @classmethod
+    def from_grid(cls, grid):
+        """a ``grid.Grid`` with both parts, which is neither uploaded nor indexed again"""
+        self = cls.__new__(cls)
+        self._on(grid)
+        return self
 
     @classmethod
     def from_dataloader(cls, loader):
         """the grid of an S^3 file (``data.Dataloader``) exported with ``interpolate_at_vertices=True``"""
-        return cls(loader.vertices, loader.levels, loader._size_initial_cell, loader.nodes, loader.faces)
+        return cls.from_grid(Grid.from_dataloader(loader))
 
     @classmethod
     def from_s_cube(cls, s_cube):
         """the grid of a ``SparseSpatialSampling`` after ``execute_grid_generation``"""
-        if getattr(s_cube, "centers", None) is None:
-            raise ValueError("the grid has not been generated yet: call execute_grid_generation() first")
-        return cls(s_cube.centers, s_cube.levels, float(s_cube.size_initial_cell), s_cube.vertices, s_cube.faces)
+        return cls.from_grid(Grid.from_s_cube(s_cube))
 
     # ---- arguments --------------------------------------------------------------------------------------------------------------
     def _velocity(self, velocity, min_snapshots):
