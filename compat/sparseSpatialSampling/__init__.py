@@ -23,6 +23,8 @@ _MODULES = {
     # the four polytope bodies live in one module here
     "geometry.triangle_geometry": "geometry.polytope_geometry", "geometry.prism_geometry": "geometry.polytope_geometry",
     "geometry.tetrahedron_geometry": "geometry.polytope_geometry", "geometry.pyramid_geometry": "geometry.polytope_geometry",
+    # no counterpart in the reference: connected regions of cell fields (``Regions``, ``RegionTable``) under the alias as well
+    "regions": "regions",
 }
 
 for _alias, _target in _MODULES.items():

@@ -415,6 +415,7 @@ int s3_grad_apply(const double *d_coef /*[n,k,dim]*/, const int32_t *d_idx /*[n,
  *     d_faces                      [n_cells][2^dim] int32, the corner nodes of every cell; NULL where no node field is read
  * An entry point that takes a grid requires: n_cells in [1, 2^31), dim 2 | 3, depth >= 0 and dim * depth <= 63, h_min > 0, width finite
  * and positive and, when there is work, every array but d_faces non-null; d_faces non-null where the mode reads node fields.
+ * Which leaf lies across each face of a cell (s3_cell_neighbours: the same-or-coarser leaf or -1) is stated with the connected regions below.
  *
  * s3_cell_index computes the keys on the device, sorts (key, cell) with s3_sort_pairs and checks that the sorted ranges are
  * disjoint.  It writes the sorted range starts, ends and cell ids (d_starts, d_ends, d_ids: n entries each) and returns when they
@@ -553,6 +554,58 @@ int s3_iso_emit(const void *d_field, int dtype, int64_t row_len, int64_t in_stri
                 int64_t n_cells, int dim, double level, const double *d_nodes /*[n_nodes,dim]*/, const int32_t *d_offset /*[row_len,n_cells]*/,
                 int64_t capacity, double *d_verts /*[capacity,dim,dim]*/, int32_t *d_edges /*[capacity,dim,2]*/, double *d_frac /*[capacity,dim]*/,
                 int32_t *d_cells /*[capacity]*/, s3_stream stream);
+
+/* ---- connected regions of thresholded cell fields (csrc/regions.hip; no counterpart in the reference) ----
+ * The grid is the s3_grid of s3_cell_index (d_faces is not read).  This text is normative.
+ *   neighbours  face f = 2 * axis + side of cell c, side 0 the lower face.  With the anchor a and the level l of c as s3_cell_index derives
+ *               them and s = 2^(L-l), the lattice cell looked up is a with a[axis] - 1 (side 0) or a[axis] + s (side 1) in place of a[axis];
+ *               a coordinate outside [0, 2^L) is the domain edge.
+ *                   nbr[c][f] = j   if a leaf j holds that lattice cell (key, binary search and range test of s3_cell_locate) and l_j <= l_c
+ *                   nbr[c][f] = -1  otherwise: the domain edge, a body or a hole, or FINER cells across the face
+ *               The table holds every pair of leaves that share a face of positive area exactly once from the finer side, and from both
+ *               sides at equal level; 2:1 balance is not assumed.  s3_cell_neighbours writes d_nbr [n_cells][2 dim] int32, one lane per cell.
+ *   in          cell c at column t iff lo <= (double) f[c][t] <= hi.  NaN is out; lo = -inf and hi = +inf are allowed, NaN bounds are not.
+ *               d_field: rows [row_len] f32 or f64 (dtype: S3_DTYPE_*) with pitch in_stride ELEMENTS (0 = row_len), read where they lie.
+ *   labels      d_labels int32 [n_cells][row_len] with pitch out_stride (0 = row_len): -1 where the cell is out, otherwise the SMALLEST cell id,
+ *               in the caller's numbering, among the in-cells connected to c at column t through pairs of the table (shared faces; edges and
+ *               corners do not connect).  A pure function of the inputs: the bits do not depend on the run, the batch split, row_len, the
+ *               pitches, d_order or the element type (an f32 field gives the bits of its f64 copy).
+ *               s3_region_label runs the phases named by `phases` (S3_REGION_ALL for a labelling; single phases for measurements), each a
+ *               launch of its own: S3_REGION_INIT labels[c][t] = in ? c : -1; S3_REGION_HOOK union-find per column on the label array itself
+ *               (for every table pair with two in-ends the larger root is hooked under the smaller one by an agent-scope compare-and-swap;
+ *               every value ever stored at (x, t) is <= x, so every chase and every retry strictly decreases: no lane waits for another);
+ *               S3_REGION_FLATTEN labels[c][t] = its root.  d_order [n_cells] or NULL: the order in which the hooking launch takes the cells
+ *               (s3_spatial_order of the centres).  No floating-point atomics.
+ *   table       a root is a (c, t) with labels[c][t] == c.  s3_region_count writes d_count[t][c] = 1 for a root, 0 otherwise (int32
+ *               [row_len][n_cells], snapshot-major); the caller scans it in place with one entry more (s3_exclusive_scan, elem_bytes 4): the
+ *               scan at [t][0] is where column t's slice of the table starts, the last entry the number of regions.  Region r of column t is
+ *               the r-th root of the column by ascending cell id.  s3_region_emit takes the scan as d_offset and writes for each of the
+ *               n_regions regions, with h = width / 2^l and V = h * h (2-D) or (h * h) * h (3-D) in f64 as written, over the cells of the region:
+ *                   d_label int32 the root; d_n_cells int64; d_volume f64 = sum V; d_centroid f64 [dim] = (sum V c) / (sum V);
+ *                   d_lo / d_hi f64 [dim] = min of c - h/2 / max of c + h/2 (f64 as written)
+ *               and with a second cell field d_weight (g; rows like d_field with pitch weight_stride; NULL: none, the three arrays are not
+ *               written): d_integral = sum V g, d_g_min / d_g_max = fmin / fmax over (double) g from +inf / -inf.
+ *               Counts, the box and the extrema are exact.  Every sum runs over the cells of the region in ascending id in a fixed order
+ *               without atomics: lane k of 16 takes the cells k, k + 16, .. (volume: adds; numerator and integral: fma(V, x, acc) from 0),
+ *               then lane += lane + 8, + 4, + 2, + 1; a region of more than 1024 cells: thread k of 256 takes the cells k, k + 256, ..,
+ *               then lane += lane + 32, .., + 1 in each of the four wavefronts, then wavefront 0 += 1, += 2, += 3.  The order depends on
+ *               the size of the region alone: equal inputs give equal bits.  A label that names no root counts as out.
+ * s3_region_label, s3_region_count and s3_region_emit refuse n_cells * row_len >= 2^31 - 1: split the batch. */
+#define S3_REGION_INIT 1
+#define S3_REGION_HOOK 2
+#define S3_REGION_FLATTEN 4
+#define S3_REGION_ALL 7
+int s3_cell_neighbours(const s3_grid *grid, int32_t *d_nbr /*[n_cells,2*dim]*/, s3_stream stream);
+int s3_region_label(const void *d_field, int dtype, int64_t row_len, int64_t in_stride, const int32_t *d_nbr /*[n_cells,2*dim]*/, int64_t n_cells,
+                    int dim, double lo, double hi, const int32_t *d_order /*[n_cells] or NULL*/, int phases, int32_t *d_labels, int64_t out_stride,
+                    s3_stream stream);
+int s3_region_count(const int32_t *d_labels, int64_t row_len, int64_t label_stride, int64_t n_cells, int32_t *d_count /*[row_len,n_cells]*/,
+                    s3_stream stream);
+int s3_region_emit(const int32_t *d_labels, int64_t row_len, int64_t label_stride, const s3_grid *grid,
+                   const int32_t *d_offset /*[row_len*n_cells+1]*/, int64_t n_regions, const void *d_weight /*or NULL*/, int dtype,
+                   int64_t weight_stride, int32_t *d_label /*[n_regions]*/, int64_t *d_n_cells /*[n_regions]*/, double *d_volume /*[n_regions]*/,
+                   double *d_centroid /*[n_regions,dim]*/, double *d_lo /*[n_regions,dim]*/, double *d_hi /*[n_regions,dim]*/,
+                   double *d_integral /*[n_regions]*/, double *d_g_min /*[n_regions]*/, double *d_g_max /*[n_regions]*/, s3_stream stream);
 
 /* ---- yardsticks of the measurement (bench.py's roofline line; no counterpart in the reference, not on any product path) ----
  * s3_yard_stream      a hand-written streaming kernel over d_src: every lane reads `reads` 16-byte vectors (coalesced) and

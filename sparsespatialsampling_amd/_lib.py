@@ -104,6 +104,11 @@ HIP_SIGNATURES = {
                          c_vp, c_vp, c_vp, c_vp, c_vp]),
     "s3_iso_count": (c_int, [c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp]),
     "s3_iso_emit": (c_int, [c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "s3_cell_neighbours": (c_int, [c_grid, c_vp, c_vp]),
+    "s3_region_label": (c_int, [c_vp, c_int, c_i64, c_i64, c_vp, c_i64, c_int, c_dbl, c_dbl, c_vp, c_int, c_vp, c_i64, c_vp]),
+    "s3_region_count": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "s3_region_emit": (c_int, [c_vp, c_i64, c_i64, c_grid, c_vp, c_i64, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                               c_vp]),
     "s3_interp": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_i64, c_i64, c_vp, c_vp]),
     "s3_snapshot_major": (c_int, [c_vp, c_i64, c_int, c_i64, c_vp, c_vp]),
     "s3_snapshot_major_as": (c_int, [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_vp]),

@@ -1,4 +1,4 @@
-// The work split of the kernels that gather rows for the points of a cloud in launch order (recon.hip, differential.hip, sample.hip, iso.hip; export.hip's
+// The work split of the kernels that gather rows for the points of a cloud in launch order (recon.hip, differential.hip, sample.hip, iso.hip, regions.hip; export.hip's
 // interp_kernel and the planned kernels use the block order alone): the XCD-aware order of the blocks and the host choice of lanes per
 // point slot, points per stage and chunks per row.  gfx950 only.
 //

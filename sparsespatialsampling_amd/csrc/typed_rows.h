@@ -1,6 +1,6 @@
 // Rows of float32 or float64 read where they lie, VEC elements per load instruction: the vector type of (T, VEC), the loads, the host
 // rule that picks VEC for a launch and the step from (dtype, VEC) at run time to <T, VEC> at compile time.  Shared by every kernel
-// family that takes a `dtype` argument (metric.hip, export.hip, recon.hip, differential.hip, sample.hip, iso.hip, and through mfma_stage.h
+// family that takes a `dtype` argument (metric.hip, export.hip, recon.hip, differential.hip, sample.hip, iso.hip, regions.hip, and through mfma_stage.h
 // svd.hip and spectral.hip).  gfx950 only.
 //
 // VEC is chosen per LAUNCH, never per lane: every vector address of a launch is the base address plus multiples of a few byte
@@ -20,6 +20,8 @@
 //   s3_gram, s3_weighted_gram,             4 / 2 / 1 by base | stride*4 [| hop*4]          always 1
 //   s3_tall_gemm and the centred GEMMs,
 //   s3_segment_dft / s3_segment_psd
+//   s3_region_label (the accesses next to      always 1                                        always 1
+//   the loads are per-element atomics)
 #ifndef S3_TYPED_ROWS_H
 #define S3_TYPED_ROWS_H
 
@@ -75,7 +77,7 @@ template <int F32, int F64> struct RowWidths { static constexpr int f32 = F32, f
 using EveryRowWidth = RowWidths<4 | 2 | 1, 2 | 1>;      // s3_row_moments, s3_interp
 using WidestRowWidth = RowWidths<4 | 1, 2 | 1>;         // s3_recon_error, s3_grad_apply, s3_cell_sample, s3_iso_*: 16-byte loads or element loads
 using StagedRowWidths = RowWidths<4 | 2 | 1, 1>;        // the f64 matrix-core kernels: float64 keeps the scalar form it always had
-using ScalarRows = RowWidths<1, 1>;                     // the element type alone
+using ScalarRows = RowWidths<1, 1>;                     // the element type alone (s3_region_label)
 
 inline size_t dtype_bytes(int dtype) { return dtype == S3_DTYPE_F32 ? sizeof(float) : sizeof(double); }
 

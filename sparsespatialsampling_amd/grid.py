@@ -1,11 +1,13 @@
 """
 One generated grid on the device, described once for everything that looks things up in it: ``sampling.Probe`` (fields at points),
-``isosurface.Isosurface`` (cuts of node fields) and ``tracing.Tracer`` (particles through node velocities) all rest on a ``Grid``.
+``isosurface.Isosurface`` (cuts of node fields), ``tracing.Tracer`` (particles through node velocities) and ``regions.Regions``
+(connected regions of cell fields) all rest on a ``Grid``.
 
 A grid has two parts, and either may be absent:
 
     the cell part       ``centers`` [Nc, d], ``levels`` [Nc] or [Nc, 1] and ``width`` (the size of the initial cell): the disjoint dyadic
-                        boxes points are located in (``index``: the ``hipops.CellIndex``, built on first use and kept)
+                        boxes points are located in (``index``: the ``hipops.CellIndex``, built on first use and kept;
+                        ``neighbours``: which leaf lies across each face, built on first use and kept)
     the corner part     ``nodes`` [Nn, d] and ``faces`` [Nc, 2^d], the corner nodes of every cell: what node fields are blended and
                         cut through; its cells need not be dyadic boxes when the cell part is absent
 
@@ -23,7 +25,7 @@ class Grid:
     """``centers``, ``levels``, ``width``, ``nodes``, ``faces`` as above, numpy or torch, host or device; arrays that lie on the device
     in the kernels' types (float64, int32) are kept, not copied.  Shapes, dtypes and the range of the face ids are checked before
     anything is uploaded: a malformed grid is a ``ValueError``.  Attributes: ``dim``, ``n_cells``, ``n_nodes`` (None without the corner
-    part), the five device arrays (None where a part is absent, ``levels`` int32 [Nc]) and ``index``."""
+    part), the five device arrays (None where a part is absent, ``levels`` int32 [Nc]), ``index`` and ``neighbours``."""
 
     def __init__(self, centers=None, levels=None, width=None, nodes=None, faces=None):
         cell_part = [v is not None for v in (centers, levels, width)]
@@ -56,7 +58,7 @@ class Grid:
             if self.n_cells and (int(faces.min()) < 0 or int(faces.max()) >= self.n_nodes):
                 raise ValueError(f"faces name nodes outside [0, {self.n_nodes})")
         self.width = None if width is None else float(width)
-        self.centers = self.levels = self.nodes = self.faces = self._index = None
+        self.centers = self.levels = self.nodes = self.faces = self._index = self._neighbours = None
         if cell_part[0]:
             self.centers, self.levels = hipops.to_device(centers, pt.float64), hipops.to_device(levels.reshape(-1), pt.int32)
         if nodes is not None:
@@ -83,3 +85,12 @@ class Grid:
                 raise ValueError("points are located in the cells of a grid: build the Grid with centers, levels and width")
             self._index = hipops.cell_index(self.centers, self.levels, self.width)
         return self._index
+
+    @property
+    def neighbours(self):
+        """the face neighbours of the cell part (``hipops.cell_neighbours``): int32 [Nc, 2 d] on the device, face ``2 * axis + side``
+        holds the same-or-coarser leaf across it or -1 (the domain edge, a body or a hole, finer cells): every pair of cells that
+        share a face stands in it once from the finer side, and from both sides at equal level"""
+        if self._neighbours is None:
+            self._neighbours = hipops.cell_neighbours(self.index)
+        return self._neighbours

@@ -647,6 +647,124 @@ def iso_extract(field, faces, nodes, level, count_only=False, count_bytes=ISO_CO
     return (offsets,) + tuple(p[0] if len(parts) == 1 else pt.cat(p) for p in zip(*parts))
 
 
+REGION_PHASES = {"init": 1, "hook": 2, "flatten": 4}     # S3_REGION_* (s3hip.h)
+REGION_PAIR_BYTES = 256 << 20                           # the largest (key, cell) array [T_b, n_cells] of one table launch: 12 bytes a pair
+REGION_FIELDS = ("label", "n_cells", "volume", "centroid", "lo", "hi", "integral", "g_min", "g_max")
+
+
+def cell_neighbours(index, out=None):
+    """the face neighbours of every cell (s3_cell_neighbours): int32 [n_cells, 2 * dim], face ``2 * axis + side`` (side 0: the lower
+    face) holds the same-or-coarser leaf across it or -1 (the domain edge, a body or a hole, finer cells).  Every pair of cells that
+    share a face stands in the table once from the finer side, and from both sides at equal level."""
+    _cell_index(index, "cell_neighbours")
+    out = _out_tensor(out, (index.n_cells, 2 * index.dim), pt.int32, index.centers.device, "cell_neighbours")
+    check(_lib.hip_lib().s3_cell_neighbours(C.byref(index.s3_grid()), _ptr(out), _stream()), "s3_cell_neighbours")
+    return out
+
+
+def _cell_rows(t, n_cells, dtypes, who, what):
+    """-> (T, pitch in elements) of a device tensor [n_cells] or [n_cells, T] of one of ``dtypes`` whose rows are read where they lie"""
+    if not (isinstance(t, pt.Tensor) and t.is_cuda and t.dtype in dtypes and 1 <= t.dim() <= 2):
+        raise TypeError(f"{who}: {what} must be a device tensor [n_cells] or [n_cells, T] of {' / '.join(str(d) for d in dtypes)}")
+    if int(t.shape[0]) != n_cells:
+        raise ValueError(f"{who}: {what} has {int(t.shape[0])} rows, the grid {n_cells} cells")
+    layout = _row_layout(t)
+    if layout is None:
+        raise TypeError(f"{who}: the rows of {what} must be contiguous (a row pitch is allowed for a 2-D tensor)")
+    if layout[0] < 1 or n_cells < 1:
+        raise ValueError(f"{who}: empty {what} {tuple(t.shape)}")
+    return layout
+
+
+def _neighbour_table(nbr, who):
+    if not (isinstance(nbr, pt.Tensor) and nbr.is_cuda and nbr.dtype == pt.int32 and nbr.is_contiguous() and nbr.dim() == 2
+            and int(nbr.shape[1]) in (4, 6)):
+        raise TypeError(f"{who}: neighbours must be a contiguous int32 device tensor [n_cells, 4 | 6]")
+    return int(nbr.shape[0]), int(nbr.shape[1]) // 2
+
+
+def region_label(field, neighbours, lo=-np.inf, hi=np.inf, order=None, out=None, phases=("init", "hook", "flatten")):
+    """connected regions of ``lo <= field <= hi`` in every column (s3_region_label).  ``field`` float32 / float64 [n_cells] or
+    [n_cells, T] on the device (rows may be pitched: read where they lie), ``neighbours`` what ``cell_neighbours`` gave.  -> int32
+    [n_cells, T]: -1 where the cell is out (NaN is out), otherwise the smallest cell id of the face-connected in-cells; written into
+    ``out`` when given (int32, rows may be pitched).  ``order`` int32 [n_cells]: the order in which the hooking launch takes the cells
+    (``spatial_order`` of the centres).  ``phases``: single launches, for measurements."""
+    n_cells, dim = _neighbour_table(neighbours, "region_label")
+    t, in_stride = _cell_rows(field, n_cells, tuple(DTYPE_CODE), "region_label", "field")
+    lo, hi = float(lo), float(hi)
+    if np.isnan(lo) or np.isnan(hi):
+        raise ValueError(f"region_label: the bounds must not be NaN, got {lo!r} and {hi!r}")
+    _launch_rows(order, n_cells, "region_label")
+    code = 0
+    for p in phases:
+        if p not in REGION_PHASES:
+            raise ValueError(f"region_label: unknown phase {p!r}, expected some of {sorted(REGION_PHASES)}")
+        code |= REGION_PHASES[p]
+    if not code:
+        raise ValueError("region_label: no phase")
+    if out is None:
+        out = pt.empty((n_cells, t), dtype=pt.int32, device=field.device)
+    if out.dim() == 1 and t == 1:
+        out = out.view(-1, 1)
+    if out.dim() != 2 or int(out.shape[1]) != t:
+        raise ValueError(f"region_label: out must be [{n_cells}, {t}], got {tuple(out.shape)}")
+    _, out_stride = _cell_rows(out, n_cells, (pt.int32,), "region_label", "out")
+    check(_lib.hip_lib().s3_region_label(C.c_void_p(field.data_ptr()), DTYPE_CODE[field.dtype], t, in_stride, _ptr(neighbours), n_cells, dim, lo, hi,
+                                         _ptr(order), code, C.c_void_p(out.data_ptr()), out_stride, _stream()), "s3_region_label")
+    return out
+
+
+def region_batch_columns(n_cells, pair_bytes=REGION_PAIR_BYTES):
+    """the snapshots one table launch may take: its (key, cell) pairs stay under ``pair_bytes`` and n_cells * T_b under 2^31 - 1"""
+    n_cells = max(int(n_cells), 1)
+    return max(1, min(int(pair_bytes) // (12 * n_cells), ((1 << 31) - 2) // n_cells))
+
+
+def region_table(labels, index, weight=None, pair_bytes=REGION_PAIR_BYTES):
+    """the regions of ``labels`` int32 [n_cells, T] (what ``region_label`` gave; rows may be pitched): count (s3_region_count), scan
+    (s3_exclusive_scan, in place), read back the totals, emit (s3_region_emit) -- in batches of ``region_batch_columns`` snapshots.
+    ``index``: the ``CellIndex`` of the grid; ``weight``: a second cell field g like the field of ``region_label``, or None.
+    -> dict: ``offsets`` int64 numpy [T + 1] (column t owns the regions [offsets[t], offsets[t + 1]), by ascending label) and on the
+    device ``label`` int32 [R], ``n_cells`` int64 [R], ``volume`` f64 [R], ``centroid`` / ``lo`` / ``hi`` f64 [R, dim], ``integral`` /
+    ``g_min`` / ``g_max`` f64 [R] (None without ``weight``).  Sums in a fixed order: equal inputs give equal bits."""
+    n_cells, dim = _cell_index(index, "region_table").n_cells, index.dim
+    if isinstance(labels, pt.Tensor) and labels.dim() == 1:
+        labels = labels.contiguous().view(-1, 1)
+    t, _ = _cell_rows(labels, n_cells, (pt.int32,), "region_table", "labels")
+    if weight is not None:
+        if isinstance(weight, pt.Tensor) and weight.dim() == 1:
+            weight = weight.contiguous().view(-1, 1)
+        if _cell_rows(weight, n_cells, tuple(DTYPE_CODE), "region_table", "weight")[0] != t:
+            raise ValueError(f"region_table: weight has {int(weight.shape[1])} columns, the labels {t}")
+    lib, dev, grid = _lib.hip_lib(), labels.device, C.byref(index.s3_grid())
+    offsets, parts = [np.zeros(1, dtype=np.int64)], []
+    step = region_batch_columns(n_cells, pair_bytes)
+    for c0 in range(0, t, step):
+        window = labels[:, c0:c0 + step]
+        t_b, stride = int(window.shape[1]), int(window.stride(0))
+        n = t_b * n_cells
+        scan = pt.empty(n + 1, dtype=pt.int32, device=dev)                      # one entry more: its scan is the total
+        scan[n:].zero_()
+        check(lib.s3_region_count(C.c_void_p(window.data_ptr()), t_b, stride, n_cells, _ptr(scan), _stream()), "s3_region_count")
+        check(lib.s3_exclusive_scan(_ptr(scan), _ptr(scan), n + 1, 4, _stream()), "s3_exclusive_scan")
+        starts = scan[::n_cells].cpu().numpy().astype(np.int64)                 # [t_b + 1] (waits for the stream)
+        offsets.append(offsets[-1][-1] + starts[1:])
+        r = int(starts[-1])
+        part = {"label": pt.empty(r, dtype=pt.int32, device=dev), "n_cells": pt.empty(r, dtype=pt.int64, device=dev),
+                "volume": pt.empty(r, dtype=pt.float64, device=dev)}
+        part.update((k, pt.empty((r, dim), dtype=pt.float64, device=dev)) for k in ("centroid", "lo", "hi"))
+        part.update((k, pt.empty(r, dtype=pt.float64, device=dev) if weight is not None else None) for k in ("integral", "g_min", "g_max"))
+        g = None if weight is None else weight[:, c0:c0 + step]
+        check(lib.s3_region_emit(C.c_void_p(window.data_ptr()), t_b, stride, grid, _ptr(scan), r,
+                                 None if g is None else C.c_void_p(g.data_ptr()), 0 if g is None else DTYPE_CODE[g.dtype],
+                                 0 if g is None else int(g.stride(0)), *(_ptr(part[k]) for k in REGION_FIELDS), _stream()), "s3_region_emit")
+        parts.append(part)
+    table = {"offsets": np.concatenate(offsets)}
+    for k in REGION_FIELDS:
+        table[k] = None if parts[0][k] is None else (parts[0][k] if len(parts) == 1 else pt.cat([p[k] for p in parts]))
+    return table
+
+
 def _pitched_matrix(t, who):
     """row pitch in elements of a 2-D f32 / f64 device matrix with unit inner stride, read where it lies"""
     layout = _row_layout(t) if t.is_cuda and t.dtype in DTYPE_CODE and t.dim() == 2 else None
