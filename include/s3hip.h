@@ -40,7 +40,7 @@ extern "C" {
 
 /* what s3_abi_version() of a library built from this header returns; the bindings refuse a library that reports another
  * number (a stale build) with the command that rebuilds it */
-#define S3_ABI_VERSION 17
+#define S3_ABI_VERSION 18
 
 typedef struct s3_knn s3_knn; /* opaque: grid-sorted copy of the original point cloud, resident in HBM */
 typedef void *s3_stream;
@@ -150,9 +150,21 @@ int s3_child_gain_reuse(const s3_knn *knn, int k, const double *d_center, const 
                         double *d_gain /*[cap]*/, double *d_scratch, const int32_t *d_parents /*or NULL*/,
                         int64_t parents_offset, double *d_child_metric /*[cap][2^dim]*/, s3_stream stream);
 
-/* a12: geometry predicates on the nodes of the listed cells (d_cells == NULL: ids first..first+n-1).  Each call ORs
- * its verdict into d_invalid[n] (zero it first): GeometryObject._apply_mask policy, geometry_base.py:40-76.
- *   box:      lo <= x <= hi in every dimension                       cube_geometry.py:50-74
+/* a12: geometry predicates on the nodes of cells.  s3_mask_cells describes the cells of a launch once, for every body; it is a
+ * plain description of memory the caller owns, read during the call only.  Each call ORs its verdict into d_invalid[n] (zero it
+ * first): GeometryObject._apply_mask policy, geometry_base.py:40-76.  Every s3_mask_* requires: a non-null struct; dim among the
+ * body's dimensions (box, sphere: 2 | 3; polygon, triangle: 2; cylinder, prism, tetrahedra, mesh: 3); n >= 0 and first >= 0;
+ * d_center, d_level and d_invalid non-null unless n == 0 (then nothing is launched).  All of it is checked before any launch. */
+typedef struct s3_mask_cells {
+    const double  *d_center;   /* [*, dim] */
+    const int32_t *d_level;    /* [*] */
+    const int32_t *d_cells;    /* [n] ordered ids, or NULL: the range first .. first+n-1 (first is ignored with a list) */
+    int64_t first, n;
+    int dim;                   /* 2 | 3 */
+    double width;              /* of the root cell */
+    uint8_t *d_invalid;        /* [n], OR-ed into */
+} s3_mask_cells;
+/*   box:      lo <= x <= hi in every dimension                       cube_geometry.py:50-74
  *   sphere:   ||x - pos|| <= radius                                  sphere_geometry.py:47-72
  *   cylinder: 0 <= proj <= norm && normal distance <= local radius   cylinder_geometry.py:126-157
  *   polygon:  strictly inside (boundary excluded)                    coordinates_2d.py:54-75
@@ -161,43 +173,35 @@ int s3_child_gain_reuse(const s3_knn *knn, int k, const double *d_center, const 
  *   tetrahedra (1 = tetrahedron, 2 = the two halves of a pyramid, union): no inward face normal sees the point
  *             behind its face                                        tetrahedron_geometry.py:121-140,
  *                                                                    pyramid_geometry.py:156-170
- *   mesh (closed triangle surface, 3-D): on the surface, or the +x ray crosses it an odd number of times -- the package's own
+ *   mesh (closed triangle surface): on the surface, or the +x ray crosses it an odd number of times -- the package's own
  *             exact rule (geometry/geometry_STL_3d.py states it per facet); stands in for vtkSelectEnclosedPoints of
  *                                                                    geometry_STL_3d.py:86-104 */
-int s3_mask_box(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n, int dim,
-                double width, const double *h_lo, const double *h_hi, int refine_mode, int keep_inside,
-                uint8_t *d_invalid, s3_stream stream);
-int s3_mask_sphere(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                   int dim, double width, const double *h_pos, double radius, int refine_mode, int keep_inside,
-                   uint8_t *d_invalid, s3_stream stream);
-int s3_mask_cylinder(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                     double width, const double *h_p0, const double *h_axis, double norm, double r0, double r1,
-                     int is_cone, int refine_mode, int keep_inside, uint8_t *d_invalid, s3_stream stream);
-int s3_mask_polygon(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                    double width, const double *d_poly /*[nv,2] device*/, int nv, int refine_mode, int keep_inside,
-                    uint8_t *d_invalid, s3_stream stream);
-int s3_mask_triangle(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                     double width, const double *h_points /*[3][2]*/, int refine_mode, int keep_inside,
-                     uint8_t *d_invalid, s3_stream stream);
-int s3_mask_prism(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                  double width, const double *h_origin /*[3] first point of the first triangle*/,
+int s3_mask_box(const s3_mask_cells *cells, const double *h_lo /*[dim]*/, const double *h_hi /*[dim]*/, int refine_mode,
+                int keep_inside, s3_stream stream);
+int s3_mask_sphere(const s3_mask_cells *cells, const double *h_pos /*[dim]*/, double radius, int refine_mode, int keep_inside,
+                   s3_stream stream);
+int s3_mask_cylinder(const s3_mask_cells *cells, const double *h_p0, const double *h_axis, double norm, double r0, double r1,
+                     int is_cone, int refine_mode, int keep_inside, s3_stream stream);
+int s3_mask_polygon(const s3_mask_cells *cells, const double *d_poly /*[nv,2] device*/, int nv, int refine_mode,
+                    int keep_inside, s3_stream stream);
+int s3_mask_triangle(const s3_mask_cells *cells, const double *h_points /*[3][2]*/, int refine_mode, int keep_inside,
+                     s3_stream stream);
+int s3_mask_prism(const s3_mask_cells *cells, const double *h_origin /*[3] first point of the first triangle*/,
                   const double *h_axis /*[3] extrusion*/, double norm, const int32_t *h_dims /*[2] in-plane axes*/,
                   const double *h_triangle /*[3][2] first triangle in those axes*/, int refine_mode, int keep_inside,
-                  uint8_t *d_invalid, s3_stream stream);
-int s3_mask_tetrahedra(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                       double width, const double *h_positions /*[n_tets][4][3]*/,
+                  s3_stream stream);
+int s3_mask_tetrahedra(const s3_mask_cells *cells, const double *h_positions /*[n_tets][4][3]*/,
                        const double *h_normals /*[n_tets][3][4] inward, column p belongs to point p*/, int n_tets,
-                       int refine_mode, int keep_inside, uint8_t *d_invalid, s3_stream stream);
+                       int refine_mode, int keep_inside, s3_stream stream);
 
 /* d_tri: facets with their vertices in lexicographic (x, y, z) order; h_lo / h_hi: bounding box of the surface (a node outside
  * it is outside before any table is read); d_bin_start / d_bin_facet: CSR lists of a uniform ny x nz grid of (y, z) columns over
  * that box, column (iy, iz) at iy*nz + iz with i = clamp(floor((v - lo) * (n / (hi - lo))), 0, n - 1) (scale 0 for a flat extent),
  * each listing every facet whose closed projected bounding box touches the column (ny = nz = 1: all facets, brute force).  One
  * lane per (cell, node); facet ids must be < nt and bin_start[ny*nz] the length of d_bin_facet (not checked on the device). */
-int s3_mask_mesh(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                 double width, const double *d_tri /*[nt][3][3]*/, int nt, const double *h_lo /*[3]*/,
+int s3_mask_mesh(const s3_mask_cells *cells, const double *d_tri /*[nt][3][3]*/, int nt, const double *h_lo /*[3]*/,
                  const double *h_hi /*[3]*/, const int32_t *d_bin_start /*[ny*nz+1]*/, const int32_t *d_bin_facet, int ny,
-                 int nz, int refine_mode, int keep_inside, uint8_t *d_invalid, s3_stream stream);
+                 int nz, int refine_mode, int keep_inside, s3_stream stream);
 
 /* bookkeeping of one refine batch on the device-resident cell arrays: parents stop being leaves, valid children
  * become leaves, invalid children get gain 0 (s_cube.py:721-723, 250-251) */

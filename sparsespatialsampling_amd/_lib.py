@@ -26,11 +26,10 @@ class S3HipError(RuntimeError):
 
 _hip = None
 _topo = None
-ABI_VERSION = 17         # S3_ABI_VERSION of include/s3hip.h this file was written against
+ABI_VERSION = 18         # S3_ABI_VERSION of include/s3hip.h this file was written against
 _REBUILD = "python -c 'import __graft_entry__ as g; g.build()'"
 
 c_i64, c_i32, c_int, c_dbl, c_vp = C.c_int64, C.c_int32, C.c_int, C.c_double, C.c_void_p
-
 
 
 class S3Grid(C.Structure):
@@ -41,6 +40,15 @@ class S3Grid(C.Structure):
 
 
 c_grid = C.POINTER(S3Grid)
+
+
+class S3MaskCells(C.Structure):
+    """``s3_mask_cells`` of include/s3hip.h: the cells of a mask launch, described once for every ``s3_mask_*``"""
+    _fields_ = [("d_center", c_vp), ("d_level", c_vp), ("d_cells", c_vp), ("first", c_i64), ("n", c_i64), ("dim", c_int),
+                ("width", c_dbl), ("d_invalid", c_vp)]
+
+
+c_mask_cells = C.POINTER(S3MaskCells)
 
 # name -> (restype, argtypes); must list every symbol include/s3hip.h declares (tests/test_abi.py checks this)
 HIP_SIGNATURES = {
@@ -75,17 +83,14 @@ HIP_SIGNATURES = {
     "s3_child_gain": (c_int, [c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_int, c_dbl, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp]),
     "s3_child_gain_reuse": (c_int, [c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_int, c_dbl, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp,
                                     c_i64, c_vp, c_vp]),
-    "s3_mask_box": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_dbl, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
-    "s3_mask_sphere": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_dbl, c_vp, c_dbl, c_int, c_int, c_vp, c_vp]),
-    "s3_mask_cylinder": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_int, c_int,
-                                 c_int, c_vp, c_vp]),
-    "s3_mask_polygon": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
-    "s3_mask_triangle": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_vp, c_int, c_int, c_vp, c_vp]),
-    "s3_mask_prism": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_vp, c_vp, c_dbl, c_vp, c_vp, c_int, c_int, c_vp,
-                              c_vp]),
-    "s3_mask_tetrahedra": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
-    "s3_mask_mesh": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
-                             c_int, c_vp, c_vp]),
+    "s3_mask_box": (c_int, [c_mask_cells, c_vp, c_vp, c_int, c_int, c_vp]),
+    "s3_mask_sphere": (c_int, [c_mask_cells, c_vp, c_dbl, c_int, c_int, c_vp]),
+    "s3_mask_cylinder": (c_int, [c_mask_cells, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_int, c_int, c_int, c_vp]),
+    "s3_mask_polygon": (c_int, [c_mask_cells, c_vp, c_int, c_int, c_int, c_vp]),
+    "s3_mask_triangle": (c_int, [c_mask_cells, c_vp, c_int, c_int, c_vp]),
+    "s3_mask_prism": (c_int, [c_mask_cells, c_vp, c_vp, c_dbl, c_vp, c_vp, c_int, c_int, c_vp]),
+    "s3_mask_tetrahedra": (c_int, [c_mask_cells, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "s3_mask_mesh": (c_int, [c_mask_cells, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "s3_commit_batch": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "s3_sumsq_leaf": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "s3_topn_scratch_bytes": (C.c_size_t, [c_i64, c_i64]),

@@ -11,6 +11,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace s3 {
@@ -34,6 +35,15 @@ __global__ void make_children_kernel(double *__restrict__ center, int32_t *__res
 #pragma unroll
     for (int j = 0; j < DIM; ++j) center[child * DIM + j] = center[p * DIM + j] + dir_comp(DIM, c, j) * off;
     level[child] = lv + 1;
+}
+
+template <int DIM>
+static int launch_children(double *center, int32_t *level, const int32_t *parents, int64_t n_par, int64_t new_index, double width,
+                           s3_stream stream) {
+    make_children_kernel<DIM><<<grid_for(n_par << DIM, 256), 256, 0, as_stream(stream)>>>(center, level, parents, n_par,
+                                                                                         new_index, 0.25 * width);
+    S3_LAUNCH_CHECK();
+    return S3_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -182,12 +192,40 @@ __global__ void mask_kernel(const double *__restrict__ center, const int32_t *__
     invalid[i] |= combine(n_in, NN, refine_mode, keep_inside);
 }
 
-static int check_mask_args(const void *center, const void *level, int64_t first, int64_t n, int dim, const void *inv,
-                           const char *who) {
-    S3_REQUIRE(dim == 2 || dim == 3, "%s: dim must be 2 or 3", who);
-    S3_REQUIRE(n >= 0 && first >= 0, "%s: bad range", who);
-    S3_REQUIRE(n == 0 || (center && level && inv), "%s: null array", who);
+// the dimensions of the cells a body masks, by its parameter type: bit d for dimension d
+constexpr int DIMS_2 = 1 << 2, DIMS_3 = 1 << 3, DIMS_2_3 = DIMS_2 | DIMS_3;
+template <typename G>
+constexpr int cell_dims() {
+    if (std::is_same_v<G, BoxParams> || std::is_same_v<G, SphereParams>) return DIMS_2_3;
+    return std::is_same_v<G, PolyParams> || std::is_same_v<G, TriParams> ? DIMS_2 : DIMS_3;
+}
+
+// what every s3_mask_* requires of its cells (include/s3hip.h); `dims`: the cell_dims of the body
+static int check_mask_cells(const char *who, const s3_mask_cells *c, int dims) {
+    S3_REQUIRE(c, "%s: null cells", who);
+    S3_REQUIRE((c->dim == 2 || c->dim == 3) && (dims >> c->dim & 1), "%s: the body has no cells of dim %d", who, c->dim);
+    S3_REQUIRE(c->n >= 0 && c->first >= 0, "%s: bad range", who);
+    S3_REQUIRE(c->n == 0 || (c->d_center && c->d_level && c->d_invalid), "%s: null array", who);
     return S3_OK;
+}
+
+template <int DIM, typename G>
+static int launch_mask_dim(const s3_mask_cells &c, const G &g, int refine_mode, int keep_inside, s3_stream stream) {
+    mask_kernel<DIM, G><<<grid_for(c.n, 256), 256, 0, as_stream(stream)>>>(c.d_center, c.d_level, c.d_cells, c.first, c.n,
+                                                                          0.5 * c.width, g, refine_mode, keep_inside, c.d_invalid);
+    S3_LAUNCH_CHECK();
+    return S3_OK;
+}
+
+// the body `g` on checked cells: nothing for no cells, else one launch in the cells' dimension
+template <typename G>
+static int launch_mask(const s3_mask_cells &c, const G &g, int refine_mode, int keep_inside, s3_stream stream) {
+    if (c.n == 0) return S3_OK;
+    if constexpr (cell_dims<G>() == DIMS_2_3)
+        return c.dim == 2 ? launch_mask_dim<2>(c, g, refine_mode, keep_inside, stream)
+                          : launch_mask_dim<3>(c, g, refine_mode, keep_inside, stream);
+    else
+        return launch_mask_dim<cell_dims<G>() == DIMS_2 ? 2 : 3>(c, g, refine_mode, keep_inside, stream);
 }
 
 // closed triangle mesh: on the surface, or an odd number of facets crossed by the ray in +x.  The rule per facet, its operations
@@ -564,128 +602,73 @@ int s3_make_children(double *d_center, int32_t *d_level, const int32_t *d_parent
     S3_REQUIRE(n_par >= 0 && new_index >= 1, "s3_make_children: bad range");
     S3_REQUIRE(n_par == 0 || (d_center && d_level && d_parents), "s3_make_children: null array");
     if (n_par == 0) return S3_OK;
-    const double qw = 0.25 * width;
-    if (dim == 2)
-        make_children_kernel<2><<<grid_for(n_par * 4, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_parents,
-                                                                                        n_par, new_index, qw);
-    else
-        make_children_kernel<3><<<grid_for(n_par * 8, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_parents,
-                                                                                        n_par, new_index, qw);
-    S3_LAUNCH_CHECK();
-    return S3_OK;
+    return dim == 2 ? launch_children<2>(d_center, d_level, d_parents, n_par, new_index, width, stream)
+                    : launch_children<3>(d_center, d_level, d_parents, n_par, new_index, width, stream);
 }
 
-int s3_mask_box(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n, int dim,
-                double width, const double *h_lo, const double *h_hi, int refine_mode, int keep_inside,
-                uint8_t *d_invalid, s3_stream stream) {
-    if (int rc = check_mask_args(d_center, d_level, first, n, dim, d_invalid, "s3_mask_box")) return rc;
+int s3_mask_box(const s3_mask_cells *cells, const double *h_lo, const double *h_hi, int refine_mode, int keep_inside,
+                s3_stream stream) {
+    if (int rc = check_mask_cells("s3_mask_box", cells, cell_dims<BoxParams>())) return rc;
     S3_REQUIRE(h_lo && h_hi, "s3_mask_box: null bounds");
-    if (n == 0) return S3_OK;
     BoxParams g{};
-    for (int j = 0; j < dim; ++j) { g.lo[j] = h_lo[j]; g.hi[j] = h_hi[j]; }
-    const double hw = 0.5 * width;
-    if (dim == 2)
-        mask_kernel<2, BoxParams><<<grid_for(n, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_cells, first, n,
-                                                                                  hw, g, refine_mode, keep_inside, d_invalid);
-    else
-        mask_kernel<3, BoxParams><<<grid_for(n, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_cells, first, n,
-                                                                                  hw, g, refine_mode, keep_inside, d_invalid);
-    S3_LAUNCH_CHECK();
-    return S3_OK;
+    for (int j = 0; j < cells->dim; ++j) { g.lo[j] = h_lo[j]; g.hi[j] = h_hi[j]; }
+    return launch_mask(*cells, g, refine_mode, keep_inside, stream);
 }
 
-int s3_mask_sphere(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                   int dim, double width, const double *h_pos, double radius, int refine_mode, int keep_inside,
-                   uint8_t *d_invalid, s3_stream stream) {
-    if (int rc = check_mask_args(d_center, d_level, first, n, dim, d_invalid, "s3_mask_sphere")) return rc;
+int s3_mask_sphere(const s3_mask_cells *cells, const double *h_pos, double radius, int refine_mode, int keep_inside,
+                   s3_stream stream) {
+    if (int rc = check_mask_cells("s3_mask_sphere", cells, cell_dims<SphereParams>())) return rc;
     S3_REQUIRE(h_pos, "s3_mask_sphere: null position");
-    if (n == 0) return S3_OK;
     SphereParams g{};
-    for (int j = 0; j < dim; ++j) g.pos[j] = h_pos[j];
+    for (int j = 0; j < cells->dim; ++j) g.pos[j] = h_pos[j];
     g.radius = radius;
-    const double hw = 0.5 * width;
-    if (dim == 2)
-        mask_kernel<2, SphereParams><<<grid_for(n, 256), 256, 0, as_stream(stream)>>>(
-            d_center, d_level, d_cells, first, n, hw, g, refine_mode, keep_inside, d_invalid);
-    else
-        mask_kernel<3, SphereParams><<<grid_for(n, 256), 256, 0, as_stream(stream)>>>(
-            d_center, d_level, d_cells, first, n, hw, g, refine_mode, keep_inside, d_invalid);
-    S3_LAUNCH_CHECK();
-    return S3_OK;
+    return launch_mask(*cells, g, refine_mode, keep_inside, stream);
 }
 
-int s3_mask_cylinder(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                     double width, const double *h_p0, const double *h_axis, double norm, double r0, double r1,
-                     int is_cone, int refine_mode, int keep_inside, uint8_t *d_invalid, s3_stream stream) {
-    if (int rc = check_mask_args(d_center, d_level, first, n, 3, d_invalid, "s3_mask_cylinder")) return rc;
+int s3_mask_cylinder(const s3_mask_cells *cells, const double *h_p0, const double *h_axis, double norm, double r0, double r1,
+                     int is_cone, int refine_mode, int keep_inside, s3_stream stream) {
+    if (int rc = check_mask_cells("s3_mask_cylinder", cells, cell_dims<CylParams>())) return rc;
     S3_REQUIRE(h_p0 && h_axis && norm > 0, "s3_mask_cylinder: bad axis");
-    if (n == 0) return S3_OK;
     CylParams g{};
     for (int j = 0; j < 3; ++j) { g.p0[j] = h_p0[j]; g.axis[j] = h_axis[j]; }
     g.norm = norm; g.r0 = r0; g.r1 = r1; g.is_cone = is_cone;
-    mask_kernel<3, CylParams><<<grid_for(n, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_cells, first, n,
-                                                                              0.5 * width, g, refine_mode, keep_inside,
-                                                                              d_invalid);
-    S3_LAUNCH_CHECK();
-    return S3_OK;
+    return launch_mask(*cells, g, refine_mode, keep_inside, stream);
 }
 
-int s3_mask_polygon(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                    double width, const double *d_poly, int nv, int refine_mode, int keep_inside, uint8_t *d_invalid,
+int s3_mask_polygon(const s3_mask_cells *cells, const double *d_poly, int nv, int refine_mode, int keep_inside,
                     s3_stream stream) {
-    if (int rc = check_mask_args(d_center, d_level, first, n, 2, d_invalid, "s3_mask_polygon")) return rc;
+    if (int rc = check_mask_cells("s3_mask_polygon", cells, cell_dims<PolyParams>())) return rc;
     S3_REQUIRE(d_poly && nv >= 3, "s3_mask_polygon: need >= 3 vertices");
-    if (n == 0) return S3_OK;
-    PolyParams g{d_poly, nv};
-    mask_kernel<2, PolyParams><<<grid_for(n, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_cells, first, n,
-                                                                               0.5 * width, g, refine_mode, keep_inside,
-                                                                               d_invalid);
-    S3_LAUNCH_CHECK();
-    return S3_OK;
+    return launch_mask(*cells, PolyParams{d_poly, nv}, refine_mode, keep_inside, stream);
 }
 
-int s3_mask_triangle(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                     double width, const double *h_points, int refine_mode, int keep_inside, uint8_t *d_invalid,
-                     s3_stream stream) {
-    if (int rc = check_mask_args(d_center, d_level, first, n, 2, d_invalid, "s3_mask_triangle")) return rc;
+int s3_mask_triangle(const s3_mask_cells *cells, const double *h_points, int refine_mode, int keep_inside, s3_stream stream) {
+    if (int rc = check_mask_cells("s3_mask_triangle", cells, cell_dims<TriParams>())) return rc;
     S3_REQUIRE(h_points != nullptr, "s3_mask_triangle: null points");
-    if (n == 0) return S3_OK;
     TriParams g{};
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 2; ++j) g.p[i][j] = h_points[2 * i + j];
-    mask_kernel<2, TriParams><<<grid_for(n, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_cells, first, n,
-                                                                              0.5 * width, g, refine_mode, keep_inside,
-                                                                              d_invalid);
-    S3_LAUNCH_CHECK();
-    return S3_OK;
+    return launch_mask(*cells, g, refine_mode, keep_inside, stream);
 }
 
-int s3_mask_prism(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                  double width, const double *h_origin, const double *h_axis, double norm, const int32_t *h_dims,
-                  const double *h_triangle, int refine_mode, int keep_inside, uint8_t *d_invalid, s3_stream stream) {
-    if (int rc = check_mask_args(d_center, d_level, first, n, 3, d_invalid, "s3_mask_prism")) return rc;
+int s3_mask_prism(const s3_mask_cells *cells, const double *h_origin, const double *h_axis, double norm, const int32_t *h_dims,
+                  const double *h_triangle, int refine_mode, int keep_inside, s3_stream stream) {
+    if (int rc = check_mask_cells("s3_mask_prism", cells, cell_dims<PrismParams>())) return rc;
     S3_REQUIRE(h_origin && h_axis && h_dims && h_triangle && norm > 0, "s3_mask_prism: bad axis");
     S3_REQUIRE(h_dims[0] >= 0 && h_dims[0] < 3 && h_dims[1] >= 0 && h_dims[1] < 3 && h_dims[0] != h_dims[1],
                "s3_mask_prism: the triangle plane must be two different coordinate directions");
-    if (n == 0) return S3_OK;
     PrismParams g{};
     for (int j = 0; j < 3; ++j) { g.origin[j] = h_origin[j]; g.axis[j] = h_axis[j]; }
     g.norm = norm; g.dims[0] = h_dims[0]; g.dims[1] = h_dims[1];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 2; ++j) g.tri.p[i][j] = h_triangle[2 * i + j];
-    mask_kernel<3, PrismParams><<<grid_for(n, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_cells, first, n,
-                                                                                0.5 * width, g, refine_mode,
-                                                                                keep_inside, d_invalid);
-    S3_LAUNCH_CHECK();
-    return S3_OK;
+    return launch_mask(*cells, g, refine_mode, keep_inside, stream);
 }
 
-int s3_mask_tetrahedra(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                       double width, const double *h_positions, const double *h_normals, int n_tets, int refine_mode,
-                       int keep_inside, uint8_t *d_invalid, s3_stream stream) {
-    if (int rc = check_mask_args(d_center, d_level, first, n, 3, d_invalid, "s3_mask_tetrahedra")) return rc;
+int s3_mask_tetrahedra(const s3_mask_cells *cells, const double *h_positions, const double *h_normals, int n_tets,
+                       int refine_mode, int keep_inside, s3_stream stream) {
+    if (int rc = check_mask_cells("s3_mask_tetrahedra", cells, cell_dims<TetParams>())) return rc;
     S3_REQUIRE(h_positions && h_normals && (n_tets == 1 || n_tets == 2), "s3_mask_tetrahedra: one or two tetrahedra");
-    if (n == 0) return S3_OK;
     TetParams g{};
     g.n_tets = n_tets;
     for (int t = 0; t < n_tets; ++t) {
@@ -694,23 +677,19 @@ int s3_mask_tetrahedra(const double *d_center, const int32_t *d_level, const int
         for (int j = 0; j < 3; ++j)
             for (int p = 0; p < 4; ++p) g.nrm[t][j][p] = h_normals[(t * 3 + j) * 4 + p];
     }
-    mask_kernel<3, TetParams><<<grid_for(n, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_cells, first, n,
-                                                                              0.5 * width, g, refine_mode, keep_inside,
-                                                                              d_invalid);
-    S3_LAUNCH_CHECK();
-    return S3_OK;
+    return launch_mask(*cells, g, refine_mode, keep_inside, stream);
 }
 
-int s3_mask_mesh(const double *d_center, const int32_t *d_level, const int32_t *d_cells, int64_t first, int64_t n,
-                 double width, const double *d_tri, int nt, const double *h_lo, const double *h_hi,
+int s3_mask_mesh(const s3_mask_cells *cells, const double *d_tri, int nt, const double *h_lo, const double *h_hi,
                  const int32_t *d_bin_start, const int32_t *d_bin_facet, int ny, int nz, int refine_mode, int keep_inside,
-                 uint8_t *d_invalid, s3_stream stream) {
-    if (int rc = check_mask_args(d_center, d_level, first, n, 3, d_invalid, "s3_mask_mesh")) return rc;
+                 s3_stream stream) {
+    if (int rc = check_mask_cells("s3_mask_mesh", cells, cell_dims<MeshParams>())) return rc;
     S3_REQUIRE(d_tri && nt >= 1 && h_lo && h_hi, "s3_mask_mesh: no facets or no bounding box");
     S3_REQUIRE(d_bin_start && d_bin_facet && ny >= 1 && nz >= 1 && (int64_t)ny * nz < ((int64_t)1 << 31),
                "s3_mask_mesh: bad column table");
-    S3_REQUIRE(n < ((int64_t)1 << 31), "s3_mask_mesh: too many cells");
-    if (n == 0) return S3_OK;
+    const s3_mask_cells &c = *cells;
+    S3_REQUIRE(c.n < ((int64_t)1 << 31), "s3_mask_mesh: too many cells");
+    if (c.n == 0) return S3_OK;
     MeshParams g{};
     g.tri = d_tri;
     g.bin_start = d_bin_start;
@@ -725,8 +704,8 @@ int s3_mask_mesh(const double *d_center, const int32_t *d_level, const int32_t *
     g.sz = (double)nz / (h_hi[2] - h_lo[2]);
     if (!std::isfinite(g.sy)) g.sy = 0.0;          // flat extent: one column
     if (!std::isfinite(g.sz)) g.sz = 0.0;
-    mask_mesh_kernel<<<grid_for(n * 8, 256), 256, 0, as_stream(stream)>>>(d_center, d_level, d_cells, first, n, 0.5 * width,
-                                                                         g, refine_mode, keep_inside, d_invalid);
+    mask_mesh_kernel<<<grid_for(c.n * 8, 256), 256, 0, as_stream(stream)>>>(c.d_center, c.d_level, c.d_cells, c.first, c.n,
+                                                                           0.5 * c.width, g, refine_mode, keep_inside, c.d_invalid);
     S3_LAUNCH_CHECK();
     return S3_OK;
 }

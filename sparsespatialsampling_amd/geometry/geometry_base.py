@@ -5,7 +5,7 @@ bodies cut out of it (``keep_inside=False``: everything inside is discarded).
 API mirror of the reference's ``geometry/geometry_base.py`` (``GeometryObject``: verdict policy ``_apply_mask`` at
 reference lines 40-76, common argument checks 78-107, abstract interface 109-222).  On the hot path the per-cell
 predicate runs on the GPU: every built-in geometry describes itself through ``kernel_spec()`` and the refine loop hands
-that description to the matching ``s3_mask_*`` kernel (include/s3hip.h).  ``check_cell`` is the host-side, single-cell
+that description to the matching ``s3_mask_*`` kernel (include/s3hip.h; ``hipops.mask_body``).  ``check_cell`` is the host-side, single-cell
 entry point with the reference's signature and truth table; a geometry without a ``kernel_spec`` is evaluated through it.
 Constructor arguments are validated from each class's declarative ``_argument_rules()``.
 """

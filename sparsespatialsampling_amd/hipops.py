@@ -40,6 +40,11 @@ def _host_f64(values, n=3):
     return a
 
 
+def _host_ptr(a):
+    """a numpy array's memory as a call argument (the pointer keeps the array alive)"""
+    return a.ctypes.data_as(C.c_void_p)
+
+
 def _row_layout(t):
     """(row_len, stride in elements) of a tensor whose leading axis is the row axis when its rows can be read where they lie:
     contiguous [n, ...], or a 2-D view with unit inner stride and a pitch >= the row length (``buf[:, a:b]``); None otherwise.
@@ -1320,65 +1325,67 @@ def child_gain_handoffs(scratch, n, dim):
     return int(rest2[1]), int(rest2[0]), int(rest[0])
 
 
-def mask_box(center, level, cells, first, n, width, lo, hi, refine_mode, keep_inside, invalid):
-    dim = int(center.shape[1])
-    lo, hi = _host_f64(lo), _host_f64(hi)
-    check(_lib.hip_lib().s3_mask_box(_ptr(center), _ptr(level), _ptr(cells), int(first), int(n), dim, float(width),
-                                     lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), int(refine_mode),
-                                     int(keep_inside), _ptr(invalid), _stream()), "s3_mask_box")
+class MaskCells:
+    """the cells of a mask launch, described once for every ``mask_*`` (``s3_mask_cells`` of include/s3hip.h): ``center`` float64
+    [rows, 2 | 3] and ``level`` int32 [rows] on the device, ``width`` of the root cell, and either ``cells`` (int32 [n] on the
+    device: ordered ids) or the id range ``first .. first + n - 1`` (``n`` None: up to the last row).  Every launch ORs its verdicts
+    into ``invalid`` uint8 [n or more] (zero it first).  Checked and turned into the C struct here once, not in every launch."""
+
+    def __init__(self, center, level, width, invalid, cells=None, first=0, n=None):
+        def array(t, dtype, least, what):               # (plain attribute reads: a refine loop builds one of these per batch)
+            if not (isinstance(t, pt.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() >= least):
+                raise TypeError(f"MaskCells: {what} must be a contiguous {dtype} device tensor of at least {least} values")
+            return t.data_ptr()
+        if not (isinstance(center, pt.Tensor) and center.dim() == 2 and int(center.shape[1]) in (2, 3)):
+            raise TypeError("MaskCells: center must be [rows, 2 | 3]")
+        rows, self.dim = int(center.shape[0]), int(center.shape[1])
+        self.n = int(len(cells) if cells is not None else (rows - first if n is None else n))
+        self._arrays = (center, level, cells, invalid)                  # the struct points into them
+        self.struct = _lib.S3MaskCells(array(center, pt.float64, rows * self.dim, "center"), array(level, pt.int32, rows, "level"),
+                                       None if cells is None else array(cells, pt.int32, self.n, "cells"), int(first), self.n, self.dim,
+                                       float(width), array(invalid, pt.uint8, self.n, "invalid"))
+        self.ref = C.byref(self.struct)
 
 
-def mask_sphere(center, level, cells, first, n, width, pos, radius, refine_mode, keep_inside, invalid):
-    dim = int(center.shape[1])
-    pos = _host_f64(pos)
-    check(_lib.hip_lib().s3_mask_sphere(_ptr(center), _ptr(level), _ptr(cells), int(first), int(n), dim, float(width),
-                                        pos.ctypes.data_as(C.c_void_p), float(radius), int(refine_mode),
-                                        int(keep_inside), _ptr(invalid), _stream()), "s3_mask_sphere")
+def mask_box(cells, lo, hi, refine_mode, keep_inside):
+    check(_lib.hip_lib().s3_mask_box(cells.ref, _host_ptr(_host_f64(lo)), _host_ptr(_host_f64(hi)), int(refine_mode), int(keep_inside),
+                                     _stream()), "s3_mask_box")
 
 
-def mask_cylinder(center, level, cells, first, n, width, p0, axis, norm, r0, r1, is_cone, refine_mode, keep_inside,
-                  invalid):
-    p0, axis = _host_f64(p0), _host_f64(axis)
-    check(_lib.hip_lib().s3_mask_cylinder(_ptr(center), _ptr(level), _ptr(cells), int(first), int(n), float(width),
-                                          p0.ctypes.data_as(C.c_void_p), axis.ctypes.data_as(C.c_void_p), float(norm),
-                                          float(r0), float(r1), int(is_cone), int(refine_mode), int(keep_inside),
-                                          _ptr(invalid), _stream()), "s3_mask_cylinder")
+def mask_sphere(cells, pos, radius, refine_mode, keep_inside):
+    check(_lib.hip_lib().s3_mask_sphere(cells.ref, _host_ptr(_host_f64(pos)), float(radius), int(refine_mode), int(keep_inside),
+                                        _stream()), "s3_mask_sphere")
 
 
-def mask_polygon(center, level, cells, first, n, width, poly_dev, refine_mode, keep_inside, invalid):
-    check(_lib.hip_lib().s3_mask_polygon(_ptr(center), _ptr(level), _ptr(cells), int(first), int(n), float(width),
-                                         _ptr(poly_dev), int(poly_dev.shape[0]), int(refine_mode), int(keep_inside),
-                                         _ptr(invalid), _stream()), "s3_mask_polygon")
+def mask_cylinder(cells, p0, axis, norm, r0, r1, is_cone, refine_mode, keep_inside):
+    check(_lib.hip_lib().s3_mask_cylinder(cells.ref, _host_ptr(_host_f64(p0)), _host_ptr(_host_f64(axis)), float(norm), float(r0),
+                                          float(r1), int(is_cone), int(refine_mode), int(keep_inside), _stream()), "s3_mask_cylinder")
 
 
-def mask_triangle(center, level, cells, first, n, width, points, refine_mode, keep_inside, invalid):
-    pts = _host_f64(points, 6)
-    check(_lib.hip_lib().s3_mask_triangle(_ptr(center), _ptr(level), _ptr(cells), int(first), int(n), float(width),
-                                          pts.ctypes.data_as(C.c_void_p), int(refine_mode), int(keep_inside),
-                                          _ptr(invalid), _stream()), "s3_mask_triangle")
+def mask_polygon(cells, poly_dev, refine_mode, keep_inside):
+    check(_lib.hip_lib().s3_mask_polygon(cells.ref, _ptr(poly_dev), int(poly_dev.shape[0]), int(refine_mode), int(keep_inside),
+                                         _stream()), "s3_mask_polygon")
 
 
-def mask_prism(center, level, cells, first, n, width, origin, axis, norm, dims, triangle, refine_mode, keep_inside,
-               invalid):
-    origin, axis, tri = _host_f64(origin), _host_f64(axis), _host_f64(triangle, 6)
-    dims = np.ascontiguousarray(dims, dtype=np.int32)
-    check(_lib.hip_lib().s3_mask_prism(_ptr(center), _ptr(level), _ptr(cells), int(first), int(n), float(width),
-                                       origin.ctypes.data_as(C.c_void_p), axis.ctypes.data_as(C.c_void_p), float(norm),
-                                       dims.ctypes.data_as(C.c_void_p), tri.ctypes.data_as(C.c_void_p),
-                                       int(refine_mode), int(keep_inside), _ptr(invalid), _stream()), "s3_mask_prism")
+def mask_triangle(cells, points, refine_mode, keep_inside):
+    check(_lib.hip_lib().s3_mask_triangle(cells.ref, _host_ptr(_host_f64(points, 6)), int(refine_mode), int(keep_inside), _stream()),
+          "s3_mask_triangle")
 
 
-def mask_tetrahedra(center, level, cells, first, n, width, positions, normals, refine_mode, keep_inside, invalid):
+def mask_prism(cells, origin, axis, norm, dims, triangle, refine_mode, keep_inside):
+    check(_lib.hip_lib().s3_mask_prism(cells.ref, _host_ptr(_host_f64(origin)), _host_ptr(_host_f64(axis)), float(norm),
+                                       _host_ptr(np.ascontiguousarray(dims, dtype=np.int32)), _host_ptr(_host_f64(triangle, 6)),
+                                       int(refine_mode), int(keep_inside), _stream()), "s3_mask_prism")
+
+
+def mask_tetrahedra(cells, positions, normals, refine_mode, keep_inside):
     """positions [n_tets, 4, 3], normals [n_tets, 3, 4] (inward; column p belongs to point p)"""
-    pos = np.ascontiguousarray(positions, dtype=np.float64)
-    nrm = np.ascontiguousarray(normals, dtype=np.float64)
+    pos, nrm = np.ascontiguousarray(positions, dtype=np.float64), np.ascontiguousarray(normals, dtype=np.float64)
     n_tets = int(pos.shape[0])
     if pos.shape != (n_tets, 4, 3) or nrm.shape != (n_tets, 3, 4):
         raise ValueError("mask_tetrahedra: positions [n_tets,4,3] and normals [n_tets,3,4] expected")
-    check(_lib.hip_lib().s3_mask_tetrahedra(_ptr(center), _ptr(level), _ptr(cells), int(first), int(n), float(width),
-                                            pos.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p), n_tets,
-                                            int(refine_mode), int(keep_inside), _ptr(invalid), _stream()),
-          "s3_mask_tetrahedra")
+    check(_lib.hip_lib().s3_mask_tetrahedra(cells.ref, _host_ptr(pos), _host_ptr(nrm), n_tets, int(refine_mode), int(keep_inside),
+                                            _stream()), "s3_mask_tetrahedra")
 
 
 class MeshTable:
@@ -1403,14 +1410,32 @@ class MeshTable:
         self.bin_facet = to_device(bin_facet if len(bin_facet) else np.zeros(1, dtype=np.int32))
 
 
-def mask_mesh(center, level, cells, first, n, width, mesh, refine_mode, keep_inside, invalid):
-    if int(center.shape[1]) != 3:
+def mask_mesh(cells, mesh, refine_mode, keep_inside):
+    if cells.dim != 3:
         raise ValueError("mask_mesh: a triangle mesh is a 3-D body")
-    check(_lib.hip_lib().s3_mask_mesh(_ptr(center), _ptr(level), _ptr(cells), int(first), int(n), float(width),
-                                      _ptr(mesh.tri), mesh.nt, mesh.lo.ctypes.data_as(C.c_void_p),
-                                      mesh.hi.ctypes.data_as(C.c_void_p), _ptr(mesh.bin_start), _ptr(mesh.bin_facet),
-                                      mesh.ny, mesh.nz, int(refine_mode), int(keep_inside), _ptr(invalid), _stream()),
-          "s3_mask_mesh")
+    check(_lib.hip_lib().s3_mask_mesh(cells.ref, _ptr(mesh.tri), mesh.nt, _host_ptr(mesh.lo), _host_ptr(mesh.hi), _ptr(mesh.bin_start),
+                                      _ptr(mesh.bin_facet), mesh.ny, mesh.nz, int(refine_mode), int(keep_inside), _stream()), "s3_mask_mesh")
+
+
+# per kind a ``kernel_spec()`` can name (its first entry; geometry/geometry_base.py lists them): the launcher, and for what a kernel
+# reads on the device the upload of the spec's operands (the vertices of a polygon, the table of a mesh)
+MASK_BODIES = {"box": mask_box, "sphere": mask_sphere, "cylinder": mask_cylinder, "polygon": mask_polygon, "triangle": mask_triangle,
+               "prism": mask_prism, "tetrahedra": mask_tetrahedra, "mesh": mask_mesh}
+MASK_UPLOADS = {"polygon": lambda xy: to_device(np.ascontiguousarray(xy, dtype=np.float64)), "mesh": MeshTable}
+
+
+def mask_operands(spec):
+    """the operands ``mask_body`` takes for a ``kernel_spec()`` -> (operands, uploaded): with ``uploaded`` they are device-resident
+    and worth keeping, once per geometry; the other kinds' pass through"""
+    upload = MASK_UPLOADS.get(spec[0])
+    return (tuple(spec[1:]), False) if upload is None else ((upload(*spec[1:]),), True)
+
+
+def mask_body(cells, kind, operands, refine_mode, keep_inside):
+    """one launch of the body ``kind`` (the first entry of a ``kernel_spec()``) with the ``operands`` of ``mask_operands``"""
+    if kind not in MASK_BODIES:
+        raise NotImplementedError(f"geometry kind {kind!r} has no device kernel")
+    MASK_BODIES[kind](cells, *operands, refine_mode, keep_inside)
 
 
 def commit_batch(leaf, gain, parents, first, n_new, invalid):

@@ -131,43 +131,21 @@ class HipTreeBackend:
             n = len(cells)
             d_cells = hipops.to_device(np.ascontiguousarray(cells, dtype=np.int32))
         invalid = pt.zeros(max(n, 1), dtype=pt.uint8, device=self.dev)
-        w = float(self.width)
+        mask_cells = hipops.MaskCells(self.center, self.level, self.width, invalid, d_cells, first, n)
         for g in geometries:
             spec = g.kernel_spec() if hasattr(g, "kernel_spec") else None
-            ki = int(g.keep_inside)
             if spec is None:
                 # no device predicate (a user-defined geometry): the reference's own protocol, check_cell(nodes, refine_geometry)
                 # per cell (s_cube.py:1816-1837), on the downloaded node coordinates
                 flags = self._mask_on_host(g, bool(refine_mode), d_cells, first, n)
                 invalid[:n] |= hipops.to_device(flags)
-            elif spec[0] == "box":
-                hipops.mask_box(self.center, self.level, d_cells, first, n, w, spec[1], spec[2], refine_mode, ki, invalid)
-            elif spec[0] == "sphere":
-                hipops.mask_sphere(self.center, self.level, d_cells, first, n, w, spec[1], spec[2], refine_mode, ki,
-                                   invalid)
-            elif spec[0] == "cylinder":
-                hipops.mask_cylinder(self.center, self.level, d_cells, first, n, w, *spec[1:], refine_mode, ki, invalid)
-            elif spec[0] == "polygon":
-                key = id(g)
-                if key not in self._poly_cache:
-                    self._poly_cache[key] = hipops.to_device(np.ascontiguousarray(spec[1], dtype=np.float64))
-                hipops.mask_polygon(self.center, self.level, d_cells, first, n, w, self._poly_cache[key], refine_mode,
-                                    ki, invalid)
-            elif spec[0] == "triangle":
-                hipops.mask_triangle(self.center, self.level, d_cells, first, n, w, spec[1], refine_mode, ki, invalid)
-            elif spec[0] == "prism":
-                hipops.mask_prism(self.center, self.level, d_cells, first, n, w, *spec[1:], refine_mode, ki, invalid)
-            elif spec[0] == "tetrahedra":
-                hipops.mask_tetrahedra(self.center, self.level, d_cells, first, n, w, spec[1], spec[2], refine_mode, ki,
-                                       invalid)
-            elif spec[0] == "mesh":
-                key = id(g)
-                if key not in self._poly_cache:
-                    self._poly_cache[key] = hipops.MeshTable(*spec[1:])
-                hipops.mask_mesh(self.center, self.level, d_cells, first, n, w, self._poly_cache[key], refine_mode, ki,
-                                 invalid)
-            else:
-                raise NotImplementedError(f"geometry kind {spec[0]!r} has no device kernel")
+                continue
+            operands = self._poly_cache.get(id(g))
+            if operands is None:
+                operands, uploaded = hipops.mask_operands(spec)
+                if uploaded:                    # (vertices of a polygon, table of a mesh: once per geometry)
+                    self._poly_cache[id(g)] = operands
+            hipops.mask_body(mask_cells, spec[0], operands, refine_mode, int(g.keep_inside))
         self._last_invalid = invalid
         return invalid[:n].cpu().numpy().astype(bool)
 

@@ -583,7 +583,7 @@ def test_masks_golden(ops):
         level = pt.zeros(len(c), dtype=pt.int32, device="cuda")
         for i in range(len(c)):
             inv = pt.zeros(1, dtype=pt.uint8, device="cuda")
-            fn(center, level, None, i, 1, 2.0 * h[i], *args, inv)
+            fn(ops.MaskCells(center, level, 2.0 * h[i], inv, None, i, 1), *args)
             out[i] = bool(inv.item())
         return out
 
@@ -622,7 +622,7 @@ def test_masks_polytopes_golden(ops, key):
             got = np.zeros(len(c), dtype=bool)
             for i in range(len(c)):                      # per-cell width: one tiny launch per cell
                 inv = pt.zeros(1, dtype=pt.uint8, device="cuda")
-                fn[spec[0]](center, level, None, i, 1, 2.0 * h[i], *spec[1:], rm, ki, inv)
+                fn[spec[0]](ops.MaskCells(center, level, 2.0 * h[i], inv, None, i, 1), *spec[1:], rm, ki)
                 got[i] = bool(inv.item())
             assert np.array_equal(got, z[f"{key}_{ki}_r{rm}"]), (key, ki, rm)
 

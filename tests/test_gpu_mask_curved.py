@@ -35,7 +35,7 @@ def lattice(ops):
 
 
 def launcher(ops, body):
-    """(function, arguments between ``width`` and the mode pair) of the kernel that masks ``body``"""
+    """(function, arguments between the cells and the mode pair) of the kernel that masks ``body``"""
     if body.kind == "sphere":
         return ops.mask_sphere, body.args
     if body.kind == "box":
@@ -45,6 +45,7 @@ def launcher(ops, body):
 
 def launch(lattice, dim, fn, args, ki, rm, cells=None, first=0, n=None, invalid=None, pad=0):
     """one launch; returns the ``n`` verdict bytes and the ``pad`` canary bytes behind them"""
+    from sparsespatialsampling_amd.hipops import MaskCells
     center, level, width, total = lattice[dim]
     d_cells = None
     if cells is not None:
@@ -53,7 +54,7 @@ def launch(lattice, dim, fn, args, ki, rm, cells=None, first=0, n=None, invalid=
     buf = pt.zeros(n + pad, dtype=pt.uint8, device="cuda") if invalid is None else pt.from_numpy(invalid.copy()).cuda()
     if pad:
         buf[n:] = CANARY
-    fn(center, level, d_cells, first, n, width, *args, rm, ki, buf)
+    fn(MaskCells(center, level, width, buf, d_cells, first, n), *args, rm, ki)
     out = buf.cpu().numpy()
     return out[:n], out[n:]
 
@@ -107,13 +108,14 @@ def test_launch_shapes_against_the_reference(ops, lattice, family):
 
 def one_cell_launches(lattice, dim, fn, args):
     """verdict byte per cell and mode pair from launches of one cell each (``n = 1``, ``first = i``), the path the goldens judge"""
+    from sparsespatialsampling_amd.hipops import MaskCells
     total = lattice[dim][3]
     center, level, width, _ = lattice[dim]
     out = {}
     for ki, rm in K.MODES:
         buf = pt.zeros(total, dtype=pt.uint8, device="cuda")
         for i in range(total):
-            fn(center, level, None, i, 1, width, *args, rm, ki, buf[i:i + 1])
+            fn(MaskCells(center, level, width, buf[i:i + 1], None, i, 1), *args, rm, ki)
         out[(ki, rm)] = buf.cpu().numpy()
         assert 0 < out[(ki, rm)].sum() < total
     return out
@@ -144,13 +146,90 @@ def test_launch_shapes_against_one_cell_launches(ops, lattice, key):
     check_launch_shapes(lattice, dim, fn, args, lambda ki, rm: single[(ki, rm)], what=key)
 
 
+def body_calls(lib, ops):
+    """per entry point: (the body's dimensions, a call with valid body arguments that takes the ``s3_mask_cells``)"""
+    import ctypes as C
+    from sparsespatialsampling_amd import geometry
+    from tests import stl_meshes as M
+    null = C.c_void_p(0)
+    zero, one = (C.c_double * 3)(0.0, 0.0, 0.0), (C.c_double * 3)(1.0, 1.0, 1.0)
+    tri, dims = (C.c_double * 6)(0.0, 0.0, 1.0, 0.0, 0.0, 1.0), (C.c_int32 * 2)(0, 1)
+    pos = (C.c_double * 12)(0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1)
+    nrm = (C.c_double * 12)(*np.eye(3, 4).ravel())
+    poly = ops.to_device(np.array([[0.0, 0.0], [1.0, 0.0], [0.0, 1.0]]))
+    mesh = ops.MeshTable(*geometry.GeometrySTL3D("cube", False, M.CUBE_STL).kernel_spec()[1:])
+    lo, hi = mesh.lo.ctypes.data_as(C.c_void_p), mesh.hi.ctypes.data_as(C.c_void_p)
+    return {"s3_mask_box": ((2, 3), lambda c: lib.s3_mask_box(c, zero, one, 0, 0, null)),
+            "s3_mask_sphere": ((2, 3), lambda c: lib.s3_mask_sphere(c, zero, 1.0, 0, 0, null)),
+            "s3_mask_cylinder": ((3,), lambda c: lib.s3_mask_cylinder(c, zero, one, 1.0, 0.5, 0.5, 0, 0, 0, null)),
+            "s3_mask_polygon": ((2,), lambda c: lib.s3_mask_polygon(c, poly.data_ptr(), 3, 0, 0, null)),
+            "s3_mask_triangle": ((2,), lambda c: lib.s3_mask_triangle(c, tri, 0, 0, null)),
+            "s3_mask_prism": ((3,), lambda c: lib.s3_mask_prism(c, zero, one, 1.0, dims, tri, 0, 0, null)),
+            "s3_mask_tetrahedra": ((3,), lambda c: lib.s3_mask_tetrahedra(c, pos, nrm, 1, 0, 0, null)),
+            "s3_mask_mesh": ((3,), lambda c: lib.s3_mask_mesh(c, mesh.tri.data_ptr(), mesh.nt, lo, hi, mesh.bin_start.data_ptr(),
+                                                               mesh.bin_facet.data_ptr(), mesh.ny, mesh.nz, 0, 0, null))}
+
+
 def test_empty_launch_with_null_arrays_is_ok(ops):
-    """``n = 0`` with null arrays returns S3_OK"""
+    """``n = 0`` with null arrays returns S3_OK: every entry point, in each of its body's dimensions"""
     import ctypes as C
     from sparsespatialsampling_amd import _lib
-    lib, null = _lib.hip_lib(), C.c_void_p(0)
-    zero, one = (C.c_double * 3)(0.0, 0.0, 0.0), (C.c_double * 3)(1.0, 1.0, 1.0)
-    for dim in (2, 3):
-        assert lib.s3_mask_sphere(null, null, null, 0, 0, dim, 1.0, zero, 1.0, 0, 0, null, null) == 0
-        assert lib.s3_mask_box(null, null, null, 0, 0, dim, 1.0, zero, one, 0, 0, null, null) == 0
-    assert lib.s3_mask_cylinder(null, null, null, 0, 0, 1.0, zero, one, 1.0, 0.5, 0.5, 0, 0, 0, null, null) == 0
+    lib = _lib.hip_lib()
+    for name, (dims, call) in body_calls(lib, ops).items():
+        for dim in dims:
+            assert call(C.byref(_lib.S3MaskCells(None, None, None, 0, 0, dim, 1.0, None))) == 0, (name, dim)
+
+
+def test_cells_of_the_wrong_dimension_are_refused(ops, lattice):
+    """a body of one dimension on four real cells of the other: an error that names the entry point, before any launch"""
+    import ctypes as C
+    from sparsespatialsampling_amd import _lib
+    lib = _lib.hip_lib()
+    for name, (dims, call) in body_calls(lib, ops).items():
+        if len(dims) == 2:
+            continue
+        dim = 5 - dims[0]
+        center, level, width, _ = lattice[dim]
+        invalid = pt.full((4,), CANARY, dtype=pt.uint8, device="cuda")
+        cells = _lib.S3MaskCells(center.data_ptr(), level.data_ptr(), None, 0, 4, dim, width, invalid.data_ptr())
+        assert call(C.byref(cells)) != 0, name
+        assert name in lib.s3_last_error().decode(), name
+        pt.cuda.synchronize()
+        assert np.all(invalid.cpu().numpy() == CANARY), f"{name}: flags written by a refused call"
+
+
+def test_null_cells_are_refused(ops):
+    """a null struct pointer: an error from the check, which runs before any launch"""
+    from sparsespatialsampling_amd import _lib
+    lib = _lib.hip_lib()
+    for name, (_, call) in body_calls(lib, ops).items():
+        assert call(None) != 0, name
+        assert name in lib.s3_last_error().decode(), name
+
+
+def test_mask_cells_refuses_short_flags(ops, lattice):
+    center, level, width, _ = lattice[2]
+    with pytest.raises(TypeError):
+        ops.MaskCells(center, level, width, pt.zeros(3, dtype=pt.uint8, device="cuda"), None, 0, 4)
+    with pytest.raises(TypeError):
+        ops.MaskCells(center, level, width, pt.zeros(3, dtype=pt.uint8, device="cuda"),
+                      pt.arange(4, dtype=pt.int32, device="cuda"))
+
+
+def test_backend_mask_of_three_bodies_is_the_or_of_each(ops, lattice):
+    """``HipTreeBackend.mask`` over [box, sphere, polytope] accumulates like three calls of one geometry each"""
+    from sparsespatialsampling_amd import geometry
+    from sparsespatialsampling_amd.tree_backend import HipTreeBackend
+    center, level, width, total = lattice[3]
+    rng = np.random.default_rng(5)
+    backend = HipTreeBackend(rng.random((64, 3)), rng.random(64), 8)
+    backend.center, backend.level, backend.width = center, level, width
+    bodies = [geometry.CubeGeometry("box", False, [0.1, 0.2, 0.3], [0.6, 0.7, 0.8]),
+              geometry.SphereGeometry("ball", False, [0.6, 0.5, 0.4], 0.45), polytope(geometry, "tet_generic", False)]
+    ids = np.arange(total - 1, -1, -3, dtype=np.int32)
+    for rm in (False, True):
+        for kw in (dict(first=0, n=total), dict(first=512, n=4), dict(cells=ids)):
+            each = [backend.mask([g], rm, **kw) for g in bodies]
+            assert kw.get("n") == 4 or (all(e.any() for e in each) and len({e.tobytes() for e in each}) == 3)
+            assert np.array_equal(backend.mask(bodies, rm, **kw), each[0] | each[1] | each[2])
+    backend.close()

@@ -41,7 +41,7 @@ def device_verdicts(ops, mesh, center, level, width, rm, ki, cells=None, first=0
         n, d_cells = len(cells), ops.to_device(np.ascontiguousarray(cells, dtype=np.int32))
     n = len(center) - first if n is None else n
     invalid = pt.zeros(n, dtype=pt.uint8, device="cuda") if preset is None else ops.to_device(preset.copy())
-    ops.mask_mesh(d_center, d_level, d_cells, first, n, width, mesh, rm, ki, invalid)
+    ops.mask_mesh(ops.MaskCells(d_center, d_level, width, invalid, d_cells, first, n), mesh, rm, ki)
     return invalid.cpu().numpy()
 
 
@@ -103,7 +103,7 @@ def test_flat_bodies_lattices_and_the_analytic_kernels(ops, tmp_path, kind):
         spec = analytic.kernel_spec()
         fn = {"tetrahedra": ops.mask_tetrahedra, "prism": ops.mask_prism, "box": ops.mask_box}[spec[0]]
         want = pt.zeros(len(center), dtype=pt.uint8, device="cuda")
-        fn(d_center, d_level, None, 0, len(center), 1.0, *spec[1:], rm, ki, want)
+        fn(ops.MaskCells(d_center, d_level, 1.0, want), *spec[1:], rm, ki)
         got = device_verdicts(ops, table(ops, body), center, level, 1.0, rm, ki)
         assert 0 < got.sum() < len(got) and np.array_equal(got, want.cpu().numpy())
 
@@ -146,8 +146,8 @@ def test_bad_arguments_are_refused(ops, tmp_path):
         ops.MeshTable(tri, lo, hi, ny, nz, bin_start[:-1], bin_facet)
     flat = pt.zeros((4, 2), dtype=pt.float64, device="cuda")
     with pytest.raises(ValueError):
-        ops.mask_mesh(flat, pt.zeros(4, dtype=pt.int32, device="cuda"), None, 0, 4, 1.0, table(ops, body), 0, 0,
-                      pt.zeros(4, dtype=pt.uint8, device="cuda"))
+        ops.mask_mesh(ops.MaskCells(flat, pt.zeros(4, dtype=pt.int32, device="cuda"), 1.0, pt.zeros(4, dtype=pt.uint8, device="cuda")),
+                      table(ops, body), 0, 0)
 
 
 # -- 13: full refine ---------------------------------------------------------------------------------------------------------------------

@@ -94,6 +94,6 @@ def test_device_kernel_against_the_table(poly_name):
     for keep_inside in (False, True):
         for refine_mode in (False, True):
             out = pt.zeros(len(rows), dtype=pt.uint8, device="cuda")
-            hipops.mask_polygon(d_center, d_level, None, 0, len(rows), root_width, poly_dev, int(refine_mode), int(keep_inside), out)
+            hipops.mask_polygon(hipops.MaskCells(d_center, d_level, root_width, out), poly_dev, int(refine_mode), int(keep_inside))
             want = [verdicts(c[3])[(keep_inside, refine_mode)] for c in rows]
             assert out.cpu().numpy().astype(bool).tolist() == want, (poly_name, keep_inside, refine_mode)

@@ -110,7 +110,7 @@ def test_device_kernel_vs_exact_winding_number(name):
         for refine_mode in (0, 1):
             for keep_inside in (0, 1):
                 flags = pt.zeros(len(centers), dtype=pt.uint8, device="cuda")
-                hipops.mask_polygon(d_center, d_level, None, 0, len(centers), 1.0, poly_dev, refine_mode, keep_inside, flags)
+                hipops.mask_polygon(hipops.MaskCells(d_center, d_level, 1.0, flags), poly_dev, refine_mode, keep_inside)
                 if not refine_mode:
                     want = inside.all(1) if not keep_inside else ~inside.any(1)
                 else:

@@ -215,6 +215,31 @@ def test_base_class_kernel_spec_defaults_to_none():
     assert g.check_cell(pt.tensor([[0.1, 0.0], [0.2, 0.0], [0.3, 1.0], [0.4, 1.0]])) is True
 
 
+def test_unknown_geometry_kind_is_refused_before_the_library_is_loaded(monkeypatch):
+    from sparsespatialsampling_amd import _lib, hipops
+    monkeypatch.setattr(_lib, "hip_lib", lambda: pytest.fail("mask_body loaded the library for a kind it does not know"))
+    with pytest.raises(NotImplementedError) as e:
+        hipops.mask_body(None, "torus", (1.0, 0.25), False, 0)
+    assert str(e.value) == "geometry kind 'torus' has no device kernel"
+
+
+def test_every_kernel_spec_kind_has_a_launcher():
+    """the dispatch table holds exactly the kinds the ``kernel_spec`` docstring lists, and every built-in geometry names one"""
+    import re
+    from inputs import POLYTOPES, naca_outline, polytope
+    from sparsespatialsampling_amd import hipops
+    from tests import stl_meshes as M
+    listed = set(re.findall(r'\(\"(\w+)\",', geometry.GeometryObject.kernel_spec.__doc__))
+    assert len(listed) == 8 and set(hipops.MASK_BODIES) == listed
+    built_in = [geometry.CubeGeometry("g", True, [0.0, 0.0], [1.0, 1.0]), geometry.SphereGeometry("g", False, [0.2, 0.2], 0.05),
+                geometry.CylinderGeometry3D("g", False, [(0.8, 1.0, -1.0), (0.8, 1.0, 1.0)], 0.15),
+                geometry.CylinderGeometry3D("g", False, [(0.4, 0.5, 0.5), (0.9, 0.5, 0.5)], [0.2, 0.05]),
+                geometry.GeometryCoordinates2D("g", False, naca_outline()), geometry.GeometrySTL3D("g", False, M.CUBE_STL)]
+    built_in += [polytope(geometry, key, False) for key in POLYTOPES]
+    assert {type(g) for g in built_in} == {getattr(geometry, name) for name in geometry.__all__ if name != "GeometryObject"}
+    assert {g.kernel_spec()[0] for g in built_in} == listed
+
+
 def test_bench_grid_sha_and_cpu_counts():
     """helpers of bench.py that need no GPU: the grid digest depends on values, dtypes and shapes of all four arrays (what two
     backends must agree on cell for cell), and the host-core report has the three counts north_star asks to be stated"""

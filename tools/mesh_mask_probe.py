@@ -90,12 +90,12 @@ def main():
             tables = {"binned": hipops.MeshTable(tri, lo, hi, ny, nz, bin_start, bin_facet),
                       "brute": hipops.MeshTable(tri, lo, hi, *build_column_bins(tri, lo, hi, 1, 1))}
             flags = {k: pt.zeros(n_cells, dtype=pt.uint8, device="cuda") for k in ("binned", "brute", "box")}
+            cells = {k: hipops.MaskCells(d_center, d_level, width, v) for k, v in flags.items()}
             row = {"facets": int(len(tri)), "table": [int(ny), int(nz)], "facets_per_column": float(len(bin_facet) / (ny * nz))}
             for name, mesh in tables.items():
                 repeats = 20 if name == "binned" or len(tri) <= 20480 else 5
-                row[name + "_ms"] = median_ms(lambda: hipops.mask_mesh(d_center, d_level, None, 0, n_cells, width, mesh, 0, 0,
-                                                                       flags[name]), repeats=repeats, warm=2)
-            row["box_ms"] = median_ms(lambda: hipops.mask_box(d_center, d_level, None, 0, n_cells, width, lo, hi, 0, 0, flags["box"]))
+                row[name + "_ms"] = median_ms(lambda: hipops.mask_mesh(cells[name], mesh, 0, 0), repeats=repeats, warm=2)
+            row["box_ms"] = median_ms(lambda: hipops.mask_box(cells["box"], lo, hi, 0, 0))
             row["tables_agree"] = bool(pt.equal(flags["binned"], flags["brute"]))
             start = time.perf_counter()
             host = tree_backend.host_mask(body, pt.from_numpy(center[:host_cells]), pt.from_numpy(level[:host_cells]), width, False)

@@ -23,7 +23,7 @@ def wrap(obj, name, label):
     setattr(obj, name, timed)
 
 
-for n in ("make_children", "child_gain", "mask_box", "mask_cylinder", "commit_batch", "sumsq_leaf", "topn_leaf", "topn_scratch", "to_device"):
+for n in ("make_children", "child_gain", "mask_body", "commit_batch", "sumsq_leaf", "topn_leaf", "topn_scratch", "to_device"):
     wrap(hipops, n, "hipops." + n)
 for n in ("update_flagged", "__isub__", "to_array", "difference_update_ids", "__len__"):
     wrap(intset.IntSet, n, "IntSet." + n)
