@@ -20,7 +20,7 @@ if _os.environ.get("S3_KEEP_RUNTIME_PINNING") != "1":
 
 from .version import __version__
 
-__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "Grid", "Probe", "Isosurface", "IsoResult", "Tracer", "Paths", "Regions", "RegionTable", "__version__"]
+__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "Grid", "Probe", "Isosurface", "IsoResult", "Tracer", "Paths", "Regions", "RegionTable", "OverlapTable", "RegionTracks", "__version__"]
 
 
 def __getattr__(name):
@@ -49,7 +49,7 @@ def __getattr__(name):
     if name in ("Tracer", "Paths"):
         from . import tracing
         return getattr(tracing, name)
-    if name in ("Regions", "RegionTable"):
+    if name in ("Regions", "RegionTable", "OverlapTable", "RegionTracks"):
         from . import regions
         return getattr(regions, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -770,6 +770,148 @@ def region_table(labels, index, weight=None, pair_bytes=REGION_PAIR_BYTES):
     return table
 
 
+OVERLAP_PASSES = {"one_key": 0, "by_b": 1, "by_ta": 2}  # S3_OVERLAP_* (s3overlap.h)
+OVERLAP_FIELDS = ("src", "dst", "n_cells", "units", "volume")
+
+
+def overlap_key_bits(n_cells, row_len):
+    """(w, tb) of include/s3overlap.h: the bits of a cell id and of a column of one batch.  One key holds (t, a, b) while
+    tb + 2 w <= 64"""
+    return max(1, (int(n_cells) - 1).bit_length()), (int(row_len) - 1).bit_length()
+
+
+def _overlap_labels(a, b, index, who):
+    """-> (a, b as [n_cells, T], T): two int32 label arrays on the device of one shape whose rows are read where they lie"""
+    n_cells = _cell_index(index, who).n_cells
+    if isinstance(a, pt.Tensor) and a.dim() == 1:
+        a = a.contiguous().view(-1, 1)
+    if isinstance(b, pt.Tensor) and b.dim() == 1:
+        b = b.contiguous().view(-1, 1)
+    t, _ = _cell_rows(a, n_cells, (pt.int32,), who, "a")
+    if _cell_rows(b, n_cells, (pt.int32,), who, "b")[0] != t:
+        raise ValueError(f"{who}: b has {int(b.shape[1])} columns, a {t}")
+    if a.device != b.device:
+        raise TypeError(f"{who}: a and b must live on one device")
+    return a, b, t
+
+
+def _overlap_pairs(keys, vals, who):
+    if not (isinstance(keys, pt.Tensor) and isinstance(vals, pt.Tensor) and keys.is_cuda and vals.is_cuda and keys.is_contiguous()
+            and vals.is_contiguous() and keys.dtype == pt.int64 and vals.dtype == pt.int32 and keys.dim() == 1 and keys.numel() == vals.numel()):
+        raise TypeError(f"{who}: contiguous int64 keys and int32 values of one length on the device required")
+    return int(keys.numel())
+
+
+def overlap_count(a, b, index, out=None):
+    """count[t][c] = 1 where cell c is in both label arrays at column t (s3_overlap_count; "in": the label names a root of its
+    array).  ``a``, ``b`` int32 [n_cells, T] on the device (rows may be pitched; two windows of one allocation are fine).  -> int32
+    [T * n_cells], snapshot-major, written into the front of ``out`` when given"""
+    a, b, t = _overlap_labels(a, b, index, "overlap_count")
+    out = _out_tensor(out, (t * index.n_cells,), pt.int32, a.device, "overlap_count", at_least=True)
+    check(_lib.hip_lib().s3_overlap_count(C.byref(index.s3_grid()), C.c_void_p(a.data_ptr()), int(a.stride(0)), C.c_void_p(b.data_ptr()),
+                                          int(b.stride(0)), t, _ptr(out), _stream()), "s3_overlap_count")
+    return out
+
+
+def overlap_emit(a, b, index, scan, keys, vals, route="one_key"):
+    """one (key, cell) pair per in-both (c, t) at its position ``scan[t][c]`` (s3_overlap_emit): ``scan`` the exclusive scan of what
+    ``overlap_count`` gave, ``keys`` int64 / ``vals`` int32 [n_pairs].  ``route``: "one_key" (key (t, a, b)), "by_b" (key (t, b): the
+    first of two sort passes) or "by_ta" (re-keys the pairs that are there to (t, a): the second)"""
+    a, b, t = _overlap_labels(a, b, index, "overlap_emit")
+    if route not in OVERLAP_PASSES:
+        raise ValueError(f"overlap_emit: unknown route {route!r}, expected one of {sorted(OVERLAP_PASSES)}")
+    n_pairs = _overlap_pairs(keys, vals, "overlap_emit")
+    if route != "by_ta" and not (isinstance(scan, pt.Tensor) and scan.is_cuda and scan.dtype == pt.int32 and scan.is_contiguous()
+                                 and scan.numel() >= t * index.n_cells):
+        raise TypeError(f"overlap_emit: scan must be a contiguous int32 device tensor of at least {t * index.n_cells} values")
+    check(_lib.hip_lib().s3_overlap_emit(C.byref(index.s3_grid()), C.c_void_p(a.data_ptr()), int(a.stride(0)), C.c_void_p(b.data_ptr()),
+                                         int(b.stride(0)), t, None if route == "by_ta" else _ptr(scan), n_pairs, OVERLAP_PASSES[route],
+                                         _ptr(keys), _ptr(vals), _stream()), "s3_overlap_emit")
+    return keys, vals
+
+
+def overlap_heads(keys, vals, index, b, two_pass=False, out=None):
+    """head[j] = 1 where the sorted pair j is the first of its (t, a, b) (s3_overlap_heads) -> int32 [n_pairs], written into the front
+    of ``out`` when given.  ``b``: the second label array of the batch (read with ``two_pass``, whose keys hold (t, a) alone)"""
+    n_pairs = _overlap_pairs(keys, vals, "overlap_heads")
+    b, _, t = _overlap_labels(b, b, index, "overlap_heads")
+    out = _out_tensor(out, (n_pairs,), pt.int32, keys.device, "overlap_heads", at_least=True)
+    check(_lib.hip_lib().s3_overlap_heads(C.byref(index.s3_grid()), _ptr(keys), _ptr(vals), n_pairs, int(bool(two_pass)), C.c_void_p(b.data_ptr()),
+                                          int(b.stride(0)), t, _ptr(out), _stream()), "s3_overlap_heads")
+    return out
+
+
+def overlap_reduce(keys, vals, index, b, edge, n_edges, two_pass=False):
+    """the edges of the sorted pairs (s3_overlap_reduce): ``edge`` int32 [n_pairs + 1], the exclusive scan of what ``overlap_heads``
+    gave with one entry more.  -> dict of device arrays ``src``, ``dst`` int32, ``n_cells`` int64, ``units`` int64 (the unsigned bits)
+    and ``volume`` f64, [n_edges] each.  Integer sums: equal inputs give equal bits"""
+    n_pairs, n_edges = _overlap_pairs(keys, vals, "overlap_reduce"), int(n_edges)
+    b, _, t = _overlap_labels(b, b, index, "overlap_reduce")
+    if not (isinstance(edge, pt.Tensor) and edge.is_cuda and edge.dtype == pt.int32 and edge.is_contiguous() and edge.numel() >= n_pairs + 1):
+        raise TypeError(f"overlap_reduce: edge must be a contiguous int32 device tensor of at least {n_pairs + 1} values")
+    if not 0 <= n_edges <= n_pairs:
+        raise ValueError(f"overlap_reduce: {n_edges} edges of {n_pairs} pairs")
+    dev = keys.device
+    out = {"src": pt.empty(n_edges, dtype=pt.int32, device=dev), "dst": pt.empty(n_edges, dtype=pt.int32, device=dev),
+           "n_cells": pt.empty(n_edges, dtype=pt.int64, device=dev), "units": pt.empty(n_edges, dtype=pt.int64, device=dev),
+           "volume": pt.empty(n_edges, dtype=pt.float64, device=dev)}
+    check(_lib.hip_lib().s3_overlap_reduce(C.byref(index.s3_grid()), _ptr(keys), _ptr(vals), n_pairs, int(bool(two_pass)), C.c_void_p(b.data_ptr()),
+                                           int(b.stride(0)), t, _ptr(edge), n_edges, *(_ptr(out[k]) for k in OVERLAP_FIELDS), _stream()),
+          "s3_overlap_reduce")
+    return out
+
+
+def overlap_table(a, b, index, pair_bytes=REGION_PAIR_BYTES, two_pass=None):
+    """the overlap table of two label arrays int32 [n_cells, T] of one grid (include/s3overlap.h): per column the pairs (a, b) of labels
+    that occur at a cell in both, by ascending (a, b).  count (s3_overlap_count), scan, read back the pairs per column, emit
+    (s3_overlap_emit), sort (s3_sort_pairs), heads (s3_overlap_heads), scan, read back the edges per column, reduce
+    (s3_overlap_reduce) -- in batches of ``region_batch_columns`` columns.  ``two_pass``: None sorts by one key where (t, a, b) fits 64
+    bits and in two stable passes (b, then (t, a)) otherwise; True / False force a route (for tests and measurements).
+    -> dict: ``offsets`` int64 numpy [T + 1] (column t owns the edges [offsets[t], offsets[t + 1])) and on the device ``src``, ``dst``
+    int32 [E], ``n_cells`` int64 [E], ``units`` int64 [E] (the unsigned bits of the volume in finest cells) and ``volume`` f64 [E]."""
+    a, b, t = _overlap_labels(a, b, index, "overlap_table")
+    n_cells, lib, dev = index.n_cells, _lib.hip_lib(), a.device
+    offsets, parts = [np.zeros(1, dtype=np.int64)], []
+    step = region_batch_columns(n_cells, pair_bytes)
+    for c0 in range(0, t, step):
+        wa, wb = a[:, c0:c0 + step], b[:, c0:c0 + step]
+        t_b = int(wa.shape[1])
+        n = t_b * n_cells
+        w, tb = overlap_key_bits(n_cells, t_b)
+        two = tb + 2 * w > 64 if two_pass is None else bool(two_pass)
+        if not two and tb + 2 * w > 64:
+            raise ValueError(f"overlap_table: (t, a, b) of {t_b} columns and {n_cells} cells does not fit one key")
+        scan = pt.empty(n + 1, dtype=pt.int32, device=dev)                      # one entry more: its scan is the total
+        scan[n:].zero_()
+        overlap_count(wa, wb, index, out=scan)
+        check(lib.s3_exclusive_scan(_ptr(scan), _ptr(scan), n + 1, 4, _stream()), "s3_exclusive_scan")
+        starts = scan[::n_cells].cpu()                                          # [t_b + 1]: the first pair of every column (waits for the stream)
+        n_pairs = int(starts[-1])
+        if n_pairs == 0:
+            offsets.append(np.full(t_b, offsets[-1][-1], dtype=np.int64))
+            continue
+        keys, vals = pt.empty(n_pairs, dtype=pt.int64, device=dev), pt.empty(n_pairs, dtype=pt.int32, device=dev)
+        if two:
+            overlap_emit(wa, wb, index, scan, keys, vals, "by_b")
+            sort_pairs(keys, vals, w)
+            overlap_emit(wa, wb, index, None, keys, vals, "by_ta")
+            sort_pairs(keys, vals, max(1, tb + w))
+        else:
+            overlap_emit(wa, wb, index, scan, keys, vals, "one_key")
+            sort_pairs(keys, vals, tb + 2 * w)
+        head = pt.empty(n_pairs + 1, dtype=pt.int32, device=dev)
+        head[n_pairs:].zero_()
+        overlap_heads(keys, vals, index, wb, two, out=head)
+        check(lib.s3_exclusive_scan(_ptr(head), _ptr(head), n_pairs + 1, 4, _stream()), "s3_exclusive_scan")
+        first = head[starts.to(dev, pt.int64)].cpu().numpy().astype(np.int64)   # [t_b + 1]: the first edge of every column
+        offsets.append(offsets[-1][-1] + first[1:])
+        parts.append(overlap_reduce(keys, vals, index, wb, head, int(first[-1]), two))
+    table = {"offsets": np.concatenate(offsets)}
+    for k, dtype in zip(OVERLAP_FIELDS, (pt.int32, pt.int32, pt.int64, pt.int64, pt.float64)):
+        table[k] = pt.empty(0, dtype=dtype, device=dev) if not parts else parts[0][k] if len(parts) == 1 else pt.cat([p[k] for p in parts])
+    return table
+
+
 def _pitched_matrix(t, who):
     """row pitch in elements of a 2-D f32 / f64 device matrix with unit inner stride, read where it lies"""
     layout = _row_layout(t) if t.is_cuda and t.dtype in DTYPE_CODE and t.dim() == 2 else None
