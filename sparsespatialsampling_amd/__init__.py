@@ -20,7 +20,7 @@ if _os.environ.get("S3_KEEP_RUNTIME_PINNING") != "1":
 
 from .version import __version__
 
-__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "Grid", "Probe", "Isosurface", "IsoResult", "Tracer", "Paths", "Regions", "RegionTable", "OverlapTable", "RegionTracks", "__version__"]
+__all__ = ["ReconstructionError", "reconstruct", "DMD", "welch", "SPOD", "Gradient", "Grid", "Probe", "Isosurface", "IsoResult", "Tracer", "Paths", "Regions", "RegionTable", "OverlapTable", "RegionTracks", "Rays", "between", "__version__"]
 
 
 def __getattr__(name):
@@ -52,4 +52,8 @@ def __getattr__(name):
     if name in ("Regions", "RegionTable", "OverlapTable", "RegionTracks"):
         from . import regions
         return getattr(regions, name)
+    if name in ("Rays", "between"):
+        # (``projection.parallel`` stays in its module: ``parallel`` is the name of the multi-GPU submodule here)
+        from . import projection
+        return getattr(projection, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

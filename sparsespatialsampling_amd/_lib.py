@@ -1,7 +1,7 @@
 """
 ctypes bindings of the two native libraries of this package:
 
-* ``libs3hip.so``  -- the MI355X (gfx950) kernels behind the C ABI declared in ``include/s3hip.h`` and ``include/s3overlap.h``
+* ``libs3hip.so``  -- the MI355X (gfx950) kernels behind the C ABI declared in ``include/s3hip.h``, ``include/s3overlap.h`` and ``include/s3rays.h``
 * ``libs3topo.so`` -- the host-side topology engine (``csrc/topology.cpp``; plain C++, no GPU)
 
 Both are built in-tree by ``__graft_entry__.build()`` (or ``python -m sparsespatialsampling_amd.build``).  There is no
@@ -179,6 +179,12 @@ OVERLAP_SIGNATURES = {
     "s3_overlap_reduce": (c_int, [c_grid, c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
+# the entry point of include/s3rays.h, exported from the same library (tests/test_ray_checker.py holds this table to the header)
+RAY_SIGNATURES = {
+    "s3_ray_integrate": (c_int, [c_int, c_grid, c_vp, c_vp, c_i64, c_vp, c_dbl, c_dbl, c_i64, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64,
+                                 c_vp, c_vp, c_vp, c_vp]),
+}
+
 TOPO_SIGNATURES = {
     "s3t_create": (c_vp, [c_int, c_dbl, c_vp]),
     "s3t_destroy": (None, [c_vp]),
@@ -249,7 +255,7 @@ def hip_lib():
             raise HipUnavailableError(f"{HIP_SO} not found -- build it with `python -c 'import __graft_entry__ as g; "
                                       f"g.build()'`.  This package has no CPU fallback.")
         try:
-            lib = _bind(_bind(C.CDLL(HIP_SO), HIP_SIGNATURES, HIP_SO), OVERLAP_SIGNATURES, HIP_SO)
+            lib = _bind(_bind(_bind(C.CDLL(HIP_SO), HIP_SIGNATURES, HIP_SO), OVERLAP_SIGNATURES, HIP_SO), RAY_SIGNATURES, HIP_SO)
         except OSError as e:
             raise HipUnavailableError(f"cannot load {HIP_SO}: {e}") from e
         if lib.s3_abi_version() != ABI_VERSION:

@@ -15,6 +15,7 @@ A grid has two parts, and either may be absent:
     tracer, iso = Tracer.from_grid(grid), Isosurface.from_grid(grid)        # one upload, one index
     probe = Probe.from_grid(grid, raster(lo, hi, (ny, nx)))
 """
+import numpy as np
 import torch as pt
 
 from . import hipops
@@ -85,6 +86,14 @@ class Grid:
                 raise ValueError("points are located in the cells of a grid: build the Grid with centers, levels and width")
             self._index = hipops.cell_index(self.centers, self.levels, self.width)
         return self._index
+
+    @property
+    def bounds(self):
+        """``(lo, hi)``, float64 [d] each on the host: the lattice domain of the index, ``origin`` and ``origin + 2^depth * h_min``, the
+        cube every leaf lies in (it may reach past the cells where the grid is no full cube)"""
+        ix = self.index
+        lo = np.array(ix.origin[:self.dim], dtype=np.float64)
+        return lo, lo + float(1 << ix.depth) * ix.h_min
 
     @property
     def neighbours(self):

@@ -561,6 +561,61 @@ def trace_path(index, faces, velocity, seeds, dt_snapshot, substeps=4, direction
                   paths, length, status, cells)
 
 
+RAY_MODES = {"cell": 0, "linear": 1}                                                            # S3_RAY_* (s3rays.h)
+RAY_STATUS = {"CROSSED": 0, "MISSED": 1, "BAD_RAY": 2, "TRUNCATED": 3, "BROKEN": 4}            # S3_RAY_* (s3rays.h)
+RAY_MAX_STEPS = 1 << 20
+
+
+def ray_integrate(index, origins, dirs, field, mode="cell", faces=None, t_range=(-np.inf, np.inf), order=None, max_steps=RAY_MAX_STEPS,
+                  out=None, length=None, segments=None, status=None):
+    """line-of-sight integrals of a grid field (s3_ray_integrate, include/s3rays.h).  ``index``: the ``CellIndex`` of the grid;
+    ``origins`` and ``dirs`` float64 [R, dim]: the rays ``x(t) = o + t d``; ``field`` float32 / float64 on the device: [rows] (one
+    snapshot), [rows, T] (rows may be pitched: read where they lie) or [rows, n_comp, T] contiguous; ``mode="cell"``: one row per
+    cell, the integral is sum value x chord; ``mode="linear"``: one row per grid NODE and ``faces`` int32 [n_cells, 2^dim] required,
+    the integral of the multilinear blend, exact per cell.  ``t_range``: the part of every ray that is integrated, in units of its
+    parameter; ``order`` int32 [R]: the launch order of the rays; a ray still walking after ``max_steps`` blocks is TRUNCATED.
+    -> (out f64 [R, n_comp, T], length f64 [R]: the length of the ray inside cells, segments int32 [R]: the cells crossed, status
+    int32 [R]: ``RAY_STATUS``), written into the tensors given.  The kernel takes up to three components per launch: a wider field
+    goes in groups."""
+    if mode not in RAY_MODES:
+        raise ValueError(f"ray_integrate: unknown mode {mode!r}, expected one of {sorted(RAY_MODES)}")
+    dim = _cell_index(index, "ray_integrate").dim
+    n_rays = _query_points(origins, dim, "ray_integrate")
+    if _query_points(dirs, dim, "ray_integrate") != n_rays:
+        raise ValueError(f"ray_integrate: {int(dirs.shape[0])} directions for {n_rays} origins")
+    if not (isinstance(field, pt.Tensor) and field.is_cuda and field.dtype in DTYPE_CODE and 1 <= field.dim() <= 3):
+        raise TypeError("ray_integrate: float32 / float64 device field [rows], [rows, T] or [rows, n_comp, T] required")
+    n_comp, t, in_stride = _field_rows(field, "ray_integrate")
+    n_rows = int(field.shape[0])
+    if t < 1 or n_comp < 1 or n_rows < 1:
+        raise ValueError(f"ray_integrate: empty field {tuple(field.shape)}")
+    if mode == "linear":
+        if faces is None:
+            raise ValueError("ray_integrate: mode 'linear' needs faces")
+        _grid_faces(faces, "ray_integrate", index)
+    else:
+        faces = None
+    _launch_rows(order, n_rays, "ray_integrate")
+    t_min, t_max = (float(v) for v in t_range)
+    if not t_min <= t_max:
+        raise ValueError(f"ray_integrate: t_range {t_range!r} is no range of the ray parameter")
+    if int(max_steps) < 1:
+        raise ValueError(f"ray_integrate: max_steps must be positive, got {max_steps}")
+    if n_rays * t >= 1 << 31:
+        raise ValueError(f"ray_integrate: {n_rays} rays x {t} columns are too many lanes for one launch")
+    out = _out_tensor(out, (n_rays, n_comp, t), pt.float64, field.device, "ray_integrate")
+    length = _out_tensor(length, (n_rays,), pt.float64, field.device, "ray_integrate", "length")
+    segments = _out_tensor(segments, (n_rays,), pt.int32, field.device, "ray_integrate", "segments")
+    status = _out_tensor(status, (n_rays,), pt.int32, field.device, "ray_integrate", "status")
+    lib, item, grid = _lib.hip_lib(), field.element_size(), C.byref(index.s3_grid(faces))
+    for c0, group in _component_groups(n_comp):
+        check(lib.s3_ray_integrate(RAY_MODES[mode], grid, _ptr(origins), _ptr(dirs), n_rays, _ptr(order), t_min, t_max, int(max_steps),
+                                   C.c_void_p(field.data_ptr() + c0 * t * item), DTYPE_CODE[field.dtype], group, t, in_stride, n_rows,
+                                   C.c_void_p(out.data_ptr() + c0 * t * 8), n_comp * t, _ptr(length), _ptr(segments), _ptr(status), _stream()),
+              "s3_ray_integrate")
+    return out, length, segments, status
+
+
 ISO_COUNT_BYTES = 256 << 20         # the largest count array [T_b, n_cells] int32 of one isosurface launch
 ISO_MAX_PRIMITIVES = {2: 2, 3: 12}  # per cell and snapshot
 
