@@ -12,12 +12,12 @@
 //                       greedily (plan_build.hip: one wavefront per 64 cells, LDS hash table of the tile's rows) into
 //                       tiles of <= 64 cells whose neighbour sets contain <= ucap (~500) distinct source rows; per tile the
 //                       distinct row ids and, per (cell, neighbour), the 16-bit position in that list are stored.
-//   kernel (per batch): one workgroup (256 threads) per tile.  For every 128-byte column chunk of the row it stages the
+//   kernel (per batch): one workgroup (512 threads) per tile.  For every 128-byte column chunk of the row it stages the
 //                       tile's distinct source rows ONCE into LDS (coalesced 128-B segments; the loads of the next two
-//                       chunks are in flight in 2 x 16 registers per lane), then every thread accumulates its cell's k
-//                       neighbours from LDS
-//                       (2 x ds_read_b128 + 8 cvt + 8 FMA per neighbour; the tile's weights and LDS positions are
-//                       staged in LDS once per tile), and writes 2 x 32 B of the f64 output row.
+//                       chunks are in flight in 2 x 8 registers per lane -- 64-cell tiles, eight lanes per cell; 2 x 16 and
+//                       four lanes per cell for 128-cell tiles), then every thread accumulates its cell's k neighbours from LDS
+//                       (ds_read_b128 + 4 cvt + 4 FMA per neighbour and 16-byte vector; the tile's weights and LDS positions
+//                       are staged in LDS once per tile), and writes its 32 B (2 x 32 B) of the f64 output row.
 //
 // HBM/L2 traffic per tile-chunk drops from n_cells*k segments to n_distinct segments (2.5-3x fewer on the cylinder3D
 // workload), which moves the kernel from the Infinity-Cache gather bound towards the HBM bound.
@@ -103,29 +103,29 @@ __device__ __forceinline__ void stage_tile_tables(const double *__restrict__ wp,
 }
 
 // the same with the LDS image laid out [m][TC] (row pitch = the tile capacity, not the tile's cell count): the accumulate
-// loop then addresses weight / position m of its cell at a CONSTANT distance m * TC from those of neighbour 0 -- immediate offsets
-// of the LDS instructions instead of a vector add per access (two of the ~20 vector instructions per neighbour).  Four neighbours
-// per pass of the 256 threads; eight loads per lane in flight.
-template <int TC>
+// loop then addresses weight / position m of its cell at a CONSTANT distance m * TC from those of neighbour 0.  BLOCK / TC neighbours
+// per pass of the BLOCK threads; eight loads per lane in flight.
+template <int TC, int BLOCK>
 __device__ __forceinline__ void stage_tile_tables_strided(const double *__restrict__ wp, const uint16_t *__restrict__ loc, int n_c, int k,
                                                           double *__restrict__ s_w, uint16_t *__restrict__ s_loc) {
-    static_assert(TC == 64, "four rows of 64 cells per pass of 256 threads");
+    static_assert(TC == 64 && BLOCK % TC == 0, "whole rows of 64 cells per pass");
+    constexpr int MPP = BLOCK / TC;                  // neighbours per pass
     const int cl = threadIdx.x & 63, m0 = threadIdx.x >> 6;
     const bool has = cl < n_c;
     constexpr int UN = 8;
-    for (int base = 0; base < k; base += 4 * UN) {
+    for (int base = 0; base < k; base += MPP * UN) {
         double wr[UN];
         uint16_t lr[UN];
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
-            const int m = base + 4 * u + m0;
+            const int m = base + MPP * u + m0;
             const int i = has && m < k ? m * n_c + cl : 0;
             wr[u] = wp[i];
             lr[u] = loc[i];
         }
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
-            const int m = base + 4 * u + m0;
+            const int m = base + MPP * u + m0;
             if (has && m < k) {
                 s_w[m * TC + cl] = wr[u];
                 s_loc[m * TC + cl] = lr[u];
@@ -440,8 +440,67 @@ __device__ __forceinline__ void tail_map(int64_t b, int64_t tiles_per_xcd, int t
     chunk1 = chunk0 + per < n_chunks ? chunk0 + per : n_chunks;
 }
 
+// (defined with the persistent kernel below, which shares them)
+template <bool BOTH>
+__device__ __forceinline__ void stream_fma_row(double wm, const float4 &a, const float4 &b, double (&acc0)[4], double (&acc1)[4]);
+template <bool BOTH>
+__device__ __forceinline__ void stream_fma_row(double wm, const double2 &a, const double2 &b, double (&acc0)[2], double (&acc1)[2]);
+
+// One 16-byte vector of a cell's chunk (the 64-cell kernels below: eight lanes per cell): acc += sum over the neighbours m = 0 .. k - 1, in that
+// order, of w_m * x_m, software-pipelined over LDS -- while neighbour m is accumulated (stream_fma_row, as in the persistent kernel)
+// the row vector of neighbour m + 1 and the table entries of the next four neighbours are on their way.  Reads are unconditional
+// with the neighbour index clamped to k - 1, so that the waits the compiler counts are the same on every path of the main loop.
+// `s_w_c` / `s_loc_c`: the cell's entries of neighbour 0 in the tile's tables, `pitch` entries between two neighbours; `s_data_v`:
+// the lane's vector of row 0 of the LDS image.
+template <typename T>
+__device__ __forceinline__ void accumulate_vector(const double *__restrict__ s_w_c, const uint16_t *__restrict__ s_loc_c,
+                                                  const typename Vec16<T>::type *__restrict__ s_data_v, int pitch, int k,
+                                                  double (&acc)[Vec16<T>::N]) {
+    using V = typename Vec16<T>::type;
+    double none[Vec16<T>::N];
+    const int k1 = k - 1;
+    // the table entries of FOUR neighbours per read: lane q of a quad (the cell's eight lanes are two quads) reads the entry of
+    // neighbour 4 g + q, the quad broadcasts it when the neighbour's turn comes -- a quarter of the table reads of eight lanes that
+    // each read their cell's entry, and the positions of a whole group are known before its first row vector is asked for.
+    // (Measured against that plain form, three builds in rotation on one device: 3.439 against 3.452 ms, faster in 6 runs of 6.)
+    const int q = threadIdx.x & 3;
+    double wc = s_w_c[min(q, k1) * pitch], wn;
+    int pc = s_loc_c[min(q, k1) * pitch], pn;
+    V xa = s_data_v[quad_bcast_i32<0>(pc) * 8], xb;
+    int m = 0;
+    for (; m + 4 <= k; m += 4) {                         // xa = row vector of neighbour m; (wc, pc) = entries of m .. m + 3
+        const int in = min(m + 4 + q, k1) * pitch;
+        wn = s_w_c[in];
+        pn = s_loc_c[in];
+        xb = s_data_v[quad_bcast_i32<1>(pc) * 8];
+        stream_fma_row<false>(quad_bcast_f64<0>(wc), xa, xa, acc, none);
+        xa = s_data_v[quad_bcast_i32<2>(pc) * 8];
+        stream_fma_row<false>(quad_bcast_f64<1>(wc), xb, xb, acc, none);
+        xb = s_data_v[quad_bcast_i32<3>(pc) * 8];
+        stream_fma_row<false>(quad_bcast_f64<2>(wc), xa, xa, acc, none);
+        xa = s_data_v[quad_bcast_i32<0>(pn) * 8];
+        stream_fma_row<false>(quad_bcast_f64<3>(wc), xb, xb, acc, none);
+        wc = wn;
+        pc = pn;
+    }
+    if (m < k) {                                         // the last one to three neighbours
+        xb = s_data_v[quad_bcast_i32<1>(pc) * 8];
+        stream_fma_row<false>(quad_bcast_f64<0>(wc), xa, xa, acc, none);
+        if (m + 1 < k) {
+            xa = s_data_v[quad_bcast_i32<2>(pc) * 8];
+            stream_fma_row<false>(quad_bcast_f64<1>(wc), xb, xb, acc, none);
+            if (m + 2 < k) stream_fma_row<false>(quad_bcast_f64<2>(wc), xa, xa, acc, none);
+        }
+    }
+}
+
+// 512 threads for both tile sizes.  128-cell tiles (one workgroup per CU): four lanes per cell, two vectors of the chunk each, sixteen
+// staging passes -- 230 / 250 VGPRs (fp32 / fp64), two waves per SIMD.  64-cell tiles (two workgroups per CU): EIGHT lanes per cell, one
+// vector each, eight passes, as in interp_planned_shift_kernel below -- half the state per lane, 126 VGPRs, four waves per SIMD
+// (`roofline.pitched_copy`, the two forms in alternation on one device: 3.18 against 3.31 ms in 5 pairs of 5).  (The second launch
+// bound is waves per SIMD.)
 template <typename T, int TC>
-__global__ void __launch_bounds__(TC * 4, 2)  // 226 VGPRs: two waves per SIMD
+__global__ void __launch_bounds__(512, TC == 64 ? 4 : 2)
 interp_planned_kernel(const int32_t *__restrict__ perm, const int32_t *__restrict__ tile_cell_begin,
                       const int32_t *__restrict__ tile_row_begin, const int32_t *__restrict__ rows,
                       const uint16_t *__restrict__ loc, const double *__restrict__ w /*plan order*/, int k, int ucap,
@@ -450,8 +509,12 @@ interp_planned_kernel(const int32_t *__restrict__ perm, const int32_t *__restric
     using V = typename Vec16<T>::type;
     constexpr int EPV = Vec16<T>::N;                 // elements per 16-byte vector
     constexpr int EPC = PL_SEG / (int)sizeof(T);     // elements per chunk
-    constexpr int BLOCK = TC * 4;                    // 4 lanes per cell
+    constexpr int LPC = TC == 64 ? 8 : 4;            // lanes per cell
+    constexpr int BLOCK = TC * LPC;
+    static_assert(BLOCK == 512, "launch_planned launches 512 threads");
     constexpr int RPP = BLOCK / 8;                   // rows staged per pass (8 lanes per 128-B segment)
+    constexpr int NP = PL_NP * TC / 128;             // staging passes: 8 * TC rows at most (plan_ucap)
+    static_assert(NP * RPP == PL_NP * TC / 2, "the passes cover the rows a tile may hold (plan_ucap)");
     extern __shared__ float4 lds_raw[];
     V *s_data = reinterpret_cast<V *>(lds_raw);                                  // [ucap][8] 16-byte vectors
     double *s_w = reinterpret_cast<double *>(lds_raw + (size_t)ucap * 8);        // [k][TC]
@@ -477,17 +540,17 @@ interp_planned_kernel(const int32_t *__restrict__ perm, const int32_t *__restric
     // the tile's weights and LDS row positions, [neighbour][cell] so that a wavefront reads consecutive words
     stage_tile_tables(w + (int64_t)c_begin * k, loc + (int64_t)c_begin * k, n_c * k, s_w, s_loc, BLOCK);
 
-    // this thread's cell: 4 lanes per cell, each lane two 16-byte vectors of the chunk (v0 and v0+4)
-    const int cl = threadIdx.x >> 2, v0 = threadIdx.x & 3;
+    // this thread's cell: 4 lanes per cell, each lane two 16-byte vectors of the chunk (v0 and v0+4), or 8 lanes with one (v0) each
+    const int cl = threadIdx.x / LPC, v0 = threadIdx.x % LPC;
     const bool has_cell = cl < n_c;
     const int64_t cell = has_cell ? perm[c_begin + cl] : 0;
 
 
-    // staging role: 8 lanes per 128-B row segment, 32 rows per pass, <= PL_NP passes.  The row ids of this lane's passes
+    // staging role: 8 lanes per 128-B row segment, 64 rows per pass, NP <= PL_NP passes.  The row ids of this lane's passes
     // are loaded once per tile; the segment loads of chunk c+1 are issued (into registers) before chunk c is accumulated
     // from LDS, so HBM latency overlaps the LDS/FMA phase.
     const int srow = threadIdx.x >> 3, svec = threadIdx.x & 7;
-    // 2 x sixteen named registers per lane (sets A and B) instead of arrays: a loop-carried local array ends up in
+    // 2 x NP named registers per lane (sets A and B) instead of arrays: a loop-carried local array ends up in
     // scratch memory.  Two chunks are kept in flight: while chunk c is accumulated from LDS, the segments of chunk c+1
     // (other set) and c+2 (the set just emptied into LDS) are on their way.
 #define S3_REP16(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
@@ -495,8 +558,8 @@ interp_planned_kernel(const int32_t *__restrict__ perm, const int32_t *__restric
 #define S3_DECL(P) const int64_t rbase##P = (int64_t)rows[r_begin + min(P * RPP + srow, n_r - 1)] * in_stride; V preA##P, preB##P;
     S3_REP16(S3_DECL)
     // (row ids are clamped to the tile's last row and the column to the row: every load is in bounds, unconditional)
-#define S3_LOAD_A(P) preA##P = *reinterpret_cast<const V *>(seg_ + rbase##P);
-#define S3_LOAD_B(P) preB##P = *reinterpret_cast<const V *>(seg_ + rbase##P);
+#define S3_LOAD_A(P) if constexpr (P < NP) preA##P = *reinterpret_cast<const V *>(seg_ + rbase##P);
+#define S3_LOAD_B(P) if constexpr (P < NP) preB##P = *reinterpret_cast<const V *>(seg_ + rbase##P);
 #define S3_ISSUE(SET, CH)                                            \
     do {                                                             \
         const int64_t c0_ = (int64_t)(CH) * EPC;                     \
@@ -504,16 +567,21 @@ interp_planned_kernel(const int32_t *__restrict__ perm, const int32_t *__restric
         const T *seg_ = data + c0_ + (ok_ ? svec : 0) * EPV;         \
         S3_REP16(S3_LOAD_##SET)                                      \
     } while (0)
-#define S3_STORE_A(P) if (P * RPP + srow < n_r) s_data[(P * RPP + srow) * 8 + svec] = preA##P;
-#define S3_STORE_B(P) if (P * RPP + srow < n_r) s_data[(P * RPP + srow) * 8 + svec] = preB##P;
+#define S3_STORE_A(P) if constexpr (P < NP) if (P * RPP + srow < n_r) s_data[(P * RPP + srow) * 8 + svec] = preA##P;
+#define S3_STORE_B(P) if constexpr (P < NP) if (P * RPP + srow < n_r) s_data[(P * RPP + srow) * 8 + svec] = preB##P;
 
-    // accumulate the k neighbours of this thread's cell from LDS and write its 2 x 32 B of the output row
+    // accumulate the k neighbours of this thread's cell from LDS and write its 2 x 32 B (eight lanes per cell: 32 B) of the output row
     auto accumulate = [&](int chunk) {
         if (!has_cell) return;
         const int64_t col0 = (int64_t)chunk * EPC;
         double acc0[EPV], acc1[EPV];
 #pragma unroll
         for (int i = 0; i < EPV; ++i) acc0[i] = acc1[i] = 0.0;
+        if constexpr (LPC == 8) {
+            accumulate_vector<T>(s_w + cl, s_loc + cl, s_data + v0, n_c, k, acc0);
+            store_piece<EPV>(out + cell * row_len + col0 + v0 * EPV, acc0, row_len - col0 - (int64_t)v0 * EPV, even_rows);
+            return;
+        }
 #pragma unroll 4
         for (int m = 0; m < k; ++m) {
             const int pos = s_loc[m * n_c + cl];
@@ -578,8 +646,17 @@ __device__ __forceinline__ float4 select16(bool c, const float4 &a, const float4
 __device__ __forceinline__ double2 select16(bool c, const double2 &a, const double2 &b) {
     return make_double2(c ? a.x : b.x, c ? a.y : b.y);
 }
+// Workgroup shape: 512 threads on the 64-cell tile, EIGHT lanes per cell and per staged row.  What a lane holds scales with its share
+// of the tile, not with the tile: eight staging passes of 64 rows (2 x 8 line registers, 8 pointers, the 8 LDS slots packed into two registers) and ONE 16-byte
+// vector of a cell's chunk (EPV accumulators) -- half of what the 256-thread form held in 236 VGPRs -- so that the kernel fits 128
+// VGPRs and two workgroups of eight waves stay resident per CU: four waves per SIMD instead of two to cover LDS round trips, f64
+// issue stalls and the other workgroup's barriers.  Plan, tiles, LDS image, lines fetched and the arithmetic per output element are
+// those of the 256-thread form.  (The second launch bound is waves per SIMD here, not workgroups per CU: 4 = a 128-VGPR budget.)
+constexpr int PLS_BLOCK = 512;     // threads of the shift kernel
+constexpr int PLS_NP = 8;          // its staging passes, of PLS_BLOCK / 8 = 64 rows
+static_assert(PLS_NP * (PLS_BLOCK / 8) == PL_NP * 32, "the passes cover the rows a tile may hold (plan_ucap)");
 template <typename T>
-__global__ void __launch_bounds__(256, 2)
+__global__ void __launch_bounds__(PLS_BLOCK, 4)
 interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__restrict__ tile_cell_begin,
                             const int32_t *__restrict__ tile_row_begin, const int32_t *__restrict__ rows,
                             const uint16_t *__restrict__ loc, const double *__restrict__ w /*plan order*/, int k, int ucap,
@@ -589,8 +666,8 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
     constexpr int TC = 64;
     constexpr int EPV = Vec16<T>::N;
     constexpr int EPC = PL_SEG / (int)sizeof(T);
-    constexpr int BLOCK = TC * 4;
-    constexpr int RPP = BLOCK / 8;
+    constexpr int BLOCK = PLS_BLOCK;                 // 8 lanes per cell
+    constexpr int RPP = BLOCK / 8;                   // rows staged per pass (8 lanes per 128-byte line)
     extern __shared__ float4 lds_raw[];
     V *s_data = reinterpret_cast<V *>(lds_raw);                                  // [ucap][8] 16-byte vectors
     double *s_w = reinterpret_cast<double *>(lds_raw + (size_t)ucap * 8);        // [k][TC]
@@ -615,37 +692,26 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
 
     // (tables at a constant pitch of TC entries: in THIS kernel -3 % per launch against the [m][n_c] layout of the kernel above,
     // 3.478 / 3.584 ms interleaved in one process; in the kernel above the same change measured +0.4 % and was not kept)
-    stage_tile_tables_strided<TC>(w + (int64_t)c_begin * k, loc + (int64_t)c_begin * k, n_c, k, s_w, s_loc);
+    stage_tile_tables_strided<TC, BLOCK>(w + (int64_t)c_begin * k, loc + (int64_t)c_begin * k, n_c, k, s_w, s_loc);
 
-    const int cl = threadIdx.x >> 2, v0 = threadIdx.x & 3;
+    // this thread's cell: 8 lanes per cell, each lane ONE 16-byte vector of the chunk -- a cell's lanes store 256 contiguous bytes
+    const int cl = threadIdx.x >> 3, v = threadIdx.x & 7;
     const bool has_cell = cl < n_c;
     const int64_t cell = has_cell ? perm[c_begin + cl] : 0;
 
     // (defined here, ahead of the staging registers: defined behind them, the fp32 build paired a row's line loads as
     // {y, z} in misaligned registers and copied them out right after the load -- a wait for a line just requested, every step)
+    const double *const s_w_c = s_w + cl;
+    const uint16_t *const s_loc_c = s_loc + cl;
+    const V *const s_data_v = s_data + v;
     auto accumulate = [&](int chunk) {
         if (!has_cell) return;
         const int64_t col0 = (int64_t)chunk * EPC;
-        double acc0[EPV], acc1[EPV];
+        double acc[EPV];
 #pragma unroll
-        for (int i = 0; i < EPV; ++i) acc0[i] = acc1[i] = 0.0;
-#pragma unroll 4
-        for (int m = 0; m < k; ++m) {
-            const int pos = s_loc[m * TC + cl];
-            const double wm = s_w[m * TC + cl];
-            const V a = s_data[pos * 8 + v0];
-            const V c = s_data[pos * 8 + v0 + 4];
-            const T *ae = reinterpret_cast<const T *>(&a);
-            const T *ce = reinterpret_cast<const T *>(&c);
-#pragma unroll
-            for (int i = 0; i < EPV; ++i) {
-                acc0[i] = fma(wm, (double)ae[i], acc0[i]);
-                acc1[i] = fma(wm, (double)ce[i], acc1[i]);
-            }
-        }
-        double *o = out + cell * row_len + col0;
-        store_piece<EPV>(o + v0 * EPV, acc0, row_len - col0 - (int64_t)v0 * EPV, even_rows);
-        store_piece<EPV>(o + (v0 + 4) * EPV, acc1, row_len - col0 - (int64_t)(v0 + 4) * EPV, even_rows);
+        for (int i = 0; i < EPV; ++i) acc[i] = 0.0;
+        accumulate_vector<T>(s_w_c, s_loc_c, s_data_v, TC, k, acc);
+        store_piece<EPV>(out + cell * row_len + col0 + v * EPV, acc, row_len - col0 - (int64_t)v * EPV, even_rows);
     };
 
     const int srow = threadIdx.x >> 3, svec = threadIdx.x & 7;
@@ -659,11 +725,14 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
     const char *const data128 = reinterpret_cast<const char *>(data) - (base & 127);
     const int j_safe = n_vec_row / 8 - 1;                        // lines 0 .. j_safe lie inside the row whatever its phase
     // per staging pass: address of this lane's vector of the row's line 0, its LDS slot, and whether the OLDER of the two
-    // lines in the registers is the one this lane contributes to an image (v >= ph)
+    // lines in the registers is the one this lane contributes to an image (v >= ph).  The LDS addresses of a lane's eight passes
+    // differ from the constant stride of RPP rows only in the slot (svec - ph) & 7: the slots, as byte offsets, are PACKED four
+    // to a register -- eight address registers would not fit the 128-VGPR budget of four waves per SIMD (fp32: 28 bytes of scratch)
+    uint32_t slots[2] = {0u, 0u};
+    const int row_last = n_r - 1;
 #define S3H_DECL(P)                                                                                              \
     const char *ptr##P; /* this lane's vector of the row's line `chunk` (the loop's current image): advanced by two lines per   \
                            iteration, so that the lines an iteration asks for sit at IMMEDIATE offsets 256 / 384 from it */  \
-    uint32_t lds##P;  /* LDS byte address of this lane's slot of the row image */                                \
     bool old##P;      /* this lane takes its vector from the OLDER of the two lines in the registers */          \
     V preA##P, preB##P;                                                                                          \
     {                                                                                                            \
@@ -671,16 +740,24 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
         const int ph_ = (int)(a_ >> 4) & 7;                                                                      \
         ptr##P = data128 + (((a_ & ~(uintptr_t)127) - base128) + 16u * (unsigned)svec) + (int64_t)chunk0 * 128;   \
         old##P = svec >= ph_;                                                                                    \
-        /* (passes beyond the tile's last row hold a copy of it and store that copy where the row itself goes) */  \
-        lds##P = (uint32_t)(min(P * RPP + srow, n_r - 1) * 8 + ((svec - ph_) & 7)) * 16u;                         \
+        slots[P >> 2] |= (uint32_t)(((svec - ph_) & 7) * 16) << (8 * (P & 3));                                   \
     }
-    S3_REP16(S3H_DECL)
+#define S3_REP8(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+    static_assert(PLS_NP == 8, "S3_REP8 expands PLS_NP staging passes");
+    S3_REP8(S3H_DECL)
     // line J of every row of this lane's passes -> register set SET.  Past j_safe the lane's vector index counted from the row
     // start (J * 8 + svec - ph) is clamped to the row's last vector.
+    // (unpacked from COPIES the compiler cannot see through -- S3H_OPAQUE, made where the values are used: whatever it can prove
+    // invariant it hoists out of the chunk loop, one register per pass again)
+#define S3H_OPAQUE                                                   \
+    int srow_ = srow;                                                \
+    uint32_t slots_[2] = {slots[0], slots[1]};                       \
+    asm volatile("" : "+v"(srow_), "+v"(slots_[0]), "+v"(slots_[1]));
+#define S3H_SLOT16(P) ((slots_[P >> 2] >> (8 * (P & 3))) & 0xffu)
 #define S3H_LOAD_FAST(SET, P) pre##SET##P = *reinterpret_cast<const V *>(ptr##P + off_);
 #define S3H_LOAD_SAFE(SET, P)                                                                                    \
     {                                                                                                            \
-        const int s_ = (int)(lds##P >> 4) & 7;           /* (svec - ph) mod 8 */                                  \
+        const int s_ = (int)S3H_SLOT16(P) >> 4;          /* (svec - ph) mod 8 */                                  \
         const int d_ = s_ <= svec ? s_ : s_ - 8;         /* svec - ph */                                          \
         const int over_ = max(0, (J_) * 8 + d_ - last_vec);                                                      \
         pre##SET##P = *reinterpret_cast<const V *>(ptr##P + off_ - 16 * (int64_t)over_);                         \
@@ -696,9 +773,10 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
         constexpr int off_ = (AHEAD) * 128;                      \
         const int J_ = (J);                                      \
         if (J_ <= j_safe) {                                      \
-            S3_REP16(S3H_LOAD_FAST_##SET)                        \
+            S3_REP8(S3H_LOAD_FAST_##SET)                        \
         } else {                                                 \
-            S3_REP16(S3H_LOAD_SAFE_##SET)                        \
+            S3H_OPAQUE                                           \
+            S3_REP8(S3H_LOAD_SAFE_##SET)                        \
         }                                                        \
     } while (0)
 #define S3H_ADVANCE(P) ptr##P += 256;
@@ -706,7 +784,9 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
     // One LDS store per row and lane behind a select of the older / newer line's vector.  (Two stores under complementary
     // lane masks instead -- no v_cndmask -- were built and measured: 3.85 against 3.51 ms; the LDS write port costs more than
     // the four vector-ALU instructions.)
-#define S3H_STORE2(P, OLD, NEW) *reinterpret_cast<V *>(lds_raw_bytes + lds##P) = select16(old##P, OLD, NEW);
+    // (passes beyond the tile's last row hold a copy of it and store that copy where the row itself goes)
+#define S3H_STORE2(P, OLD, NEW) \
+    *reinterpret_cast<V *>(lds_raw_bytes + (uint32_t)min(P * RPP + srow_, row_last) * 128u + S3H_SLOT16(P)) = select16(old##P, OLD, NEW);
 #define S3H_STORE_AB(P) S3H_STORE2(P, preA##P, preB##P)
 #define S3H_STORE_BA(P) S3H_STORE2(P, preB##P, preA##P)
 
@@ -722,22 +802,31 @@ interp_planned_shift_kernel(const int32_t *__restrict__ perm, const int32_t *__r
         S3H_ISSUE(B, chunk0 + 1, 1);
     }
     for (int chunk = chunk0; chunk < chunk1; chunk += 2) {
-        S3_REP16(S3H_STORE_AB)
+        {
+            S3H_OPAQUE
+            S3_REP8(S3H_STORE_AB)
+        }
         __syncthreads();
         if (chunk + 1 < chunk1) S3H_ISSUE(A, chunk + 2, 2);
         accumulate(chunk);
         __syncthreads();
         if (chunk + 1 >= chunk1) break;
-        S3_REP16(S3H_STORE_BA)
+        {
+            S3H_OPAQUE
+            S3_REP8(S3H_STORE_BA)
+        }
         __syncthreads();
         if (chunk + 2 < chunk1) S3H_ISSUE(B, chunk + 3, 3);
         accumulate(chunk + 1);
         __syncthreads();
-        S3_REP16(S3H_ADVANCE)
+        S3_REP8(S3H_ADVANCE)
     }
+#undef S3_REP8
 #undef S3H_ADVANCE
 #undef S3H_DECL
 #undef S3H_LOAD_FAST
+#undef S3H_SLOT16
+#undef S3H_OPAQUE
 #undef S3H_LOAD_SAFE
 #undef S3H_LOAD_FAST_A
 #undef S3H_LOAD_FAST_B
@@ -1127,7 +1216,7 @@ constexpr int SHORT_ROW_VECS = 4;
 // fewest workgroups a launch of the chunk kernel should have before the column chunks are split over blockIdx.y
 constexpr int64_t PLAN_MIN_BLOCKS = 2048;
 
-// distinct rows a tile of `tc` cells may hold: what is left of the LDS budget (80 KiB -> two 256-thread workgroups per CU
+// distinct rows a tile of `tc` cells may hold: what is left of the LDS budget (80 KiB -> two workgroups per CU
 // for tc = 64; 160 KiB -> one 512-thread workgroup per CU for tc = 128) after the tile's weights and positions
 static int plan_ucap(int k, int tc) {
     const int budget = (tc == 128 ? 160 : 80) * 1024;
@@ -1436,9 +1525,9 @@ static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows
     if (r.route == S3_ROUTE_SHIFT) {
         auto kern = interp_planned_shift_kernel<T>;
         S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        kern<<<grid, 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,
-                                     static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles, tiles_per_xcd,
-                                     r.chunks_per_block, r.n_chunks, r.tail_tiles, r.tail_split);
+        kern<<<grid, PLS_BLOCK, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,
+                                           static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles, tiles_per_xcd,
+                                           r.chunks_per_block, r.n_chunks, r.tail_tiles, r.tail_split);
         S3_LAUNCH_CHECK();
         return S3_OK;
     }
@@ -1451,7 +1540,7 @@ static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows
     } else {
         auto kern = interp_planned_kernel<T, 64>;
         S3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        kern<<<grid, 256, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,
+        kern<<<grid, 512, lds, st>>>(p->perm, p->tile_cell_begin, p->tile_row_begin, rows, p->loc, p->wp, p->k, p->ucap,
                                      static_cast<const T *>(data), row_len, in_stride, out, p->n_tiles, tiles_per_xcd,
                                      r.chunks_per_block, r.n_chunks, r.tail_tiles, r.tail_split);
     }
@@ -1463,7 +1552,8 @@ static int launch_planned(s3_interp_plan *p, const int32_t *rows, int64_t n_rows
 // The LOADS of a tile plan and nothing else: one workgroup per tile at the headline kernel's occupancy (256 threads, two per CU, the
 // same dynamic LDS), eight lanes per 128-byte line, sixteen passes of 32 rows, whole aligned lines of the rows where they lie, two
 // register sets of sixteen vectors rolling -- the shift kernel's load schedule with the LDS image, the conversions, the FMAs and the
-// stores taken away.  What it measures is the time the memory system needs for the bytes this plan STAGES (halo included), i.e. the
+// stores taken away (the schedule of that kernel's 256-thread form; the kernel now spreads the same loads per workgroup over 512
+// threads, eight passes of 64 rows).  What it measures is the time the memory system needs for the bytes this plan STAGES (halo included), i.e. the
 // floor of the tiling on this table.  VARIANT 0: every visit of a row fetches ONE line (sets = {all rows} x {line c}, {all rows} x
 // {line c + 1}: the schedule of interp_planned_shift_kernel).  VARIANT 1: every visit fetches TWO consecutive lines = 256 contiguous
 // bytes, one address translation (sets = {rows of passes 0-7} x {lines c, c + 1}, {rows of passes 8-15} x {lines c, c + 1}): the
